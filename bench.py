@@ -24,8 +24,35 @@ per step). The raw completion count and completions/s are also reported.
 TTFT samples come only from requests admitted after the turnover ramp
 (steady-state admissions), never from the synchronized initial burst.
 
+A plain run does only what the headline figure needs: engine set-up, the
+turnover ramp, --warmup steps, the --steps timed steps, the optional
+output dump and the one JSON result line. Everything else this benchmark
+may grow (baselines, other precisions or sizes, per-kernel figures) belongs
+behind --full, which is off by default; today nothing else is measured, so
+--full runs the same thing.
+
+--dump-outputs DIR writes, after the timed steps, what the timed path
+handed its caller in the last timed step that delivered tokens, as
+DIR/<name>.npy (ranks > 0 append _rank<R> to the name):
+  last_step_request_index    [n]     float64, N of request id "req-N"
+  last_step_new_token_ids    [n, k]  float64, tokens emitted that step (-1 pad)
+  last_step_output_token_ids [n, L]  float64, all tokens so far (-1 pad)
+  last_step_finished         [n]     float64, 1.0 where the request finished
+  last_logits_request_index  [m]     float64, request of each logits row
+  last_logits_sample         [m, C]  float32, the logits of the last
+                                     sampling call in the window at a fixed
+                                     seeded sample of C <= 4096 vocab columns
+Prompts, generation lengths and weights are seeded, and request "req-N"
+always carries the N-th generated prompt. The one wall-clock input of the
+engine is the scheduler's admission aging window, so with --dump-outputs
+(and no explicit --admission-ms) admission is made count-based only: a
+held prompt is released by the token threshold or an idle decode set,
+never by its age. The schedule, and with it the dumped step, is then the
+same from run to run, and two builds can be compared output for output.
+
 Usage:
   python bench.py --gpus 1 --steps 64 --warmup 16
+  python bench.py --gpus 1 --steps 64 --warmup 16 --dump-outputs bench_out
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 bench.py --gpus N --steps K --warmup W
 """
@@ -70,6 +97,14 @@ def parse_args():
                         "length, and make prompts locally repetitive so the "
                         "prompt-lookup proposer has matches (spec-decode "
                         "workload mode; headline stays spec-off)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last timed "
+                        "step's outputs as DIR/<name>.npy (see module "
+                        "docstring); makes prompt admission count-based "
+                        "so the schedule is reproducible")
+    p.add_argument("--full", action="store_true",
+                   help="also run every secondary measurement or check "
+                        "(none today: the plain run is the whole benchmark)")
     return p.parse_args()
 
 
@@ -178,6 +213,11 @@ def main():
     mc = get_model_config(args.model)
     mc.quantization = args.quantization
     max_len = args.prompt_len + args.gen_len + 64
+    admission_ms = args.admission_ms
+    if args.dump_outputs is not None and admission_ms is None:
+        # reproducible schedule: no prompt is ever released by wall-clock
+        # age (a negative --admission-ms keeps the adaptive window)
+        admission_ms = 1e12
     cfg = EngineConfig(
         model=mc,
         cache=CacheConfig(
@@ -190,8 +230,8 @@ def main():
             max_num_batched_tokens=args.max_batched_tokens,
             max_model_len=max_len,
             **({"prefill_admission_ms": (
-                None if args.admission_ms < 0 else args.admission_ms)}
-               if args.admission_ms is not None else {}),
+                None if admission_ms < 0 else admission_ms)}
+               if admission_ms is not None else {}),
         ),
         parallel=ParallelConfig(
             tensor_parallel_size=args.tp, rank=rank, world_size=world
@@ -230,6 +270,9 @@ def main():
         repetitive=args.spec_tokens > 0,
     )
     load.top_up()
+    # a plain run executes the untapped engine; the taps only exist when
+    # their result is going to be written
+    tap = _tap_engine(engine) if args.dump_outputs else None
 
     def barrier_sync():
         if distributed:
@@ -259,6 +302,8 @@ def main():
     completed_before = len(load.completion_times)
     tokens_before = engine.num_generated_tokens
     ttft_mark = len(load.ttfts)
+    if tap is not None:
+        tap["outs"] = []
     for _ in range(args.steps):
         load.step()
     barrier_sync()
@@ -271,6 +316,9 @@ def main():
     ttfts = load.ttfts[ttft_mark:]
     if len(ttfts) < 16:
         ttfts = load.ttfts[steady_ttft_mark:]
+
+    if args.dump_outputs:
+        _dump_outputs(args.dump_outputs, rank, tap)
 
     engine.stop_workers()
     spec_stats = None
@@ -288,6 +336,72 @@ def main():
                           is_driver=True, spec_stats=spec_stats)
     if distributed:
         dist.destroy_process_group()
+
+
+def _tap_engine(engine):
+    """Keep references to what the engine last handed its caller: the
+    outputs of the most recent step() that delivered any, and the logits
+    (with their row -> request map) of the most recent sampling call. No
+    copy, no sync: each tap costs the timed path one Python call per step."""
+    tap = {"outs": [], "logits": None, "req": None}
+    step = engine.step
+    sample = engine.sampler.sample
+
+    def tapped_step():
+        outs = step()
+        if outs:
+            tap["outs"] = outs
+        return outs
+
+    def tapped(logits, seqs):
+        tap["logits"] = logits
+        tap["req"] = [s.seq_id for s in seqs]
+        return sample(logits, seqs)
+
+    engine.step = tapped_step
+    engine.sampler.sample = tapped
+    return tap
+
+
+def _req_index(request_id) -> float:
+    return float(str(request_id).rsplit("-", 1)[-1])
+
+
+def _dump_outputs(out_dir, rank, tap, max_cols=4096):
+    import numpy as np
+
+    outs = tap["outs"]
+
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f"_rank{rank}" if rank else ""
+
+    def save(name, arr):
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), arr)
+
+    def padded(rows):
+        width = max((len(r) for r in rows), default=0)
+        arr = np.full((len(rows), width), -1.0, dtype=np.float64)
+        for i, r in enumerate(rows):
+            arr[i, :len(r)] = r
+        return arr
+
+    save("last_step_request_index",
+         np.array([_req_index(o.request_id) for o in outs], dtype=np.float64))
+    save("last_step_new_token_ids", padded([o.new_token_ids for o in outs]))
+    save("last_step_output_token_ids",
+         padded([o.output_token_ids for o in outs]))
+    save("last_step_finished",
+         np.array([float(o.finished) for o in outs], dtype=np.float64))
+    if tap["logits"] is not None:
+        logits = tap["logits"]
+        vocab = logits.shape[-1]
+        cols = torch.randperm(
+            vocab, generator=torch.Generator().manual_seed(4242)
+        )[:max_cols].sort().values
+        sample = logits.index_select(-1, cols.to(logits.device))
+        save("last_logits_request_index",
+             np.array([_req_index(r) for r in tap["req"]], dtype=np.float64))
+        save("last_logits_sample", sample.float().cpu().numpy())
 
 
 def _aggregate_and_report(args, rank, world, distributed, device, use_cuda,
@@ -327,7 +441,7 @@ def _aggregate_and_report(args, rank, world, distributed, device, use_cuda,
         "n_gpus": world if distributed else args.gpus,
         "steps": args.steps,
         "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1000.0, 3),
+        "ms_per_step": round(elapsed / max(args.steps, 1) * 1000.0, 3),
         "higher_is_better": True,
         "scaling": "weak",
         "vs_baseline": None,

@@ -140,5 +140,11 @@ class EngineConfig:
     # device-resident cap and total (host-parked) cap
     max_loras: int = 8
     max_cpu_loras: int = 16
+    # Batched multi-LoRA slot table (opt-in): `max_loras` stacked adapter
+    # slots of rank `max_lora_rank` (rounded up to 16) at stable device
+    # addresses, applied by the HIP lora_apply kernels and replayed under
+    # hipGraph decode. False keeps the per-adapter torch loop everywhere.
+    enable_lora: bool = False
+    max_lora_rank: int = 64
     seed: int = 0
     enforce_eager: bool = False            # True disables hipGraph decode capture

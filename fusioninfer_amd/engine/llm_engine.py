@@ -170,6 +170,7 @@ class LLMEngine:
                 max_loras=self.cfg.max_loras,
                 max_cpu_loras=self.cfg.max_cpu_loras,
                 device=self.device,
+                slots=self.runner.lora_slots,
             )
         return self.runner.lora_registry
 

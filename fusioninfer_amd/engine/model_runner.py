@@ -5,7 +5,9 @@ are captured once per batch-size bucket into hipGraphs
 (torch.cuda.CUDAGraph == hipGraph on ROCm) and replayed — removing launch
 overhead from the latency-critical decode loop (guide: "capture
 launch-bound inner loops in hipGraphs"). Prefill and mixed steps run
-eager; batches with live LoRA adapters also run eager. Payloads are plain
+eager. Decode batches with live LoRA adapters replay a second graph set
+when every adapter sits in the slot table (enable_lora); otherwise they
+run eager on the per-adapter torch loop. Payloads are plain
 host lists so the TP driver can broadcast them to worker ranks.
 
 Capability parity: the execution layer of the continuous-batching
@@ -92,6 +94,20 @@ class ModelRunner:
         self._graph_pool = None
         self._static: Dict[str, torch.Tensor] = {}
         self.lora_registry = None  # set by the engine when LoRA is enabled
+        # enable_lora: stacked adapter slots, allocated here (before
+        # allocate_kv_caches) so KV sizing sees the memory
+        self.lora_slots = None
+        self._lora_graphs: Dict[int, Tuple[object, torch.Tensor]] = {}
+        self.num_lora_graph_replays = 0  # decode steps replayed with adapters
+        self.num_lora_eager_steps = 0    # decode steps with adapters run eager
+        self.num_lora_slot_steps = 0     # steps (any kind) on the slot kernels
+        self.num_lora_loop_steps = 0     # steps on the per-adapter torch loop
+        if cfg.enable_lora and mc.quantization != "fp8":
+            from fusioninfer_amd.lora import LoRASlots
+
+            self.lora_slots = LoRASlots(
+                mc, cfg.max_loras, cfg.max_lora_rank, device=self.device
+            )
 
     # ------------------------------------------------------------ kv cache
     def kv_block_bytes(self) -> int:
@@ -198,33 +214,76 @@ class ModelRunner:
             "lora_names": [s.lora_name for s in seqs],
         }
 
-    def _lora_batch(self, prefill_payload, decode_payload, np_=0):
-        """Group this step's token rows by adapter -> LoRABatch or None."""
+    def _lora_route(self, prefill_payload, decode_payload, np_=0):
+        """Route this step's token rows to adapters. Returns None (no
+        adapter row), ("slots", host int32 [T] slot ids, -1 = base row) or
+        ("loop", [(adapter, row list)]).
+
+        The slot form needs the slot table (enable_lora), every referenced
+        adapter slot-resident, and at most max_loras distinct adapters;
+        otherwise the whole step takes the per-adapter torch loop."""
         if self.lora_registry is None:
             return None
-        groups: Dict[str, List[int]] = {}
+        spans: List[Tuple[int, int, str]] = []  # [row0, row1) -> adapter
+        total = 0
         if prefill_payload is not None:
             cu = prefill_payload["cu"]
+            total = cu[-1]
             for i, name in enumerate(prefill_payload.get("lora_names") or []):
                 if name:
-                    groups.setdefault(name, []).extend(
-                        range(cu[i], cu[i + 1])
-                    )
+                    spans.append((cu[i], cu[i + 1], name))
         if decode_payload is not None:
+            total = np_ + len(decode_payload["lens"])
             for i, name in enumerate(decode_payload.get("lora_names") or []):
                 if name:
-                    groups.setdefault(name, []).append(np_ + i)
-        if not groups:
+                    spans.append((np_ + i, np_ + i + 1, name))
+        if not spans:
             return None
+        reg = self.lora_registry
+        adapters = {}
+        for _, _, name in spans:
+            if name not in adapters:
+                adapters[name] = reg.get(name)  # LRU touch + page-in
+        if self.lora_slots is not None and len(adapters) <= reg.max_loras:
+            slot = {name: reg.slot_of(name) for name in adapters}
+            if all(s is not None for s in slot.values()):
+                ids = np.full(total, -1, dtype=np.int32)
+                for a, b, name in spans:
+                    ids[a:b] = slot[name]
+                self.num_lora_slot_steps += 1
+                return "slots", ids
+        groups: Dict[str, List[int]] = {}
+        for a, b, name in spans:
+            groups.setdefault(name, []).extend(range(a, b))
+        self.num_lora_loop_steps += 1
+        return "loop", [(adapters[n], rows) for n, rows in groups.items()]
+
+    def _lora_batch(self, prefill_payload, decode_payload, np_=0):
+        """This step's LoRABatch (slot form or per-adapter groups) or None."""
+        route = self._lora_route(prefill_payload, decode_payload, np_)
+        if route is None:
+            return None
+        from fusioninfer_amd.lora import LoRABatch
+
+        kind, data = route
+        if kind == "slots":
+            # one host-to-device copy for the whole step
+            return LoRABatch(
+                slot_ids=torch.from_numpy(data).to(self.device),
+                slots=self.lora_slots,
+            )
+        return self._lora_batch_from_groups(data)
+
+    def _lora_batch_from_groups(self, groups):
         from fusioninfer_amd.lora import LoRABatch
 
         return LoRABatch(
             [
                 (
-                    self.lora_registry.get(name),
+                    adapter,
                     torch.tensor(rows, dtype=torch.long, device=self.device),
                 )
-                for name, rows in groups.items()
+                for adapter, rows in groups
             ]
         )
 
@@ -624,6 +683,12 @@ class ModelRunner:
             ),
             "seq_lens": torch.ones(max_bs, dtype=torch.int32, device=dev),
         }
+        if self.lora_slots is not None:
+            # per-row adapter slot (-1 = base / padding row); the LoRA
+            # decode graphs read it in place
+            self._static["lora_slots"] = torch.full(
+                (max_bs,), -1, dtype=torch.int32, device=dev
+            )
 
     def _decode_forward(self, bs: int, lora=None) -> torch.Tensor:
         s = self._static
@@ -669,6 +734,23 @@ class ModelRunner:
                     with torch.cuda.graph(g, pool=self._graph_pool):
                         out = self._decode_forward(bs)
                 self._graphs[bs] = (g, out)
+            if self.lora_slots is not None and self.lora_slots.usable:
+                # second set for steps with a slot-form LoRABatch: same
+                # pool, lora_apply indexed by the static slot-id buffer.
+                # Base-only steps keep replaying the graphs above.
+                from fusioninfer_amd.lora import LoRABatch
+
+                for bs in reversed(buckets):
+                    lb = LoRABatch(
+                        slot_ids=self._static["lora_slots"][:bs],
+                        slots=self.lora_slots,
+                    )
+                    self._decode_forward(bs, lora=lb)
+                    torch.cuda.synchronize()
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g, pool=self._graph_pool):
+                        out = self._decode_forward(bs, lora=lb)
+                    self._lora_graphs[bs] = (g, out)
         torch.cuda.synchronize()
 
     def build_decode_payload(self, seqs: List[Sequence], bm: BlockManager):
@@ -743,18 +825,37 @@ class ModelRunner:
         n = len(payload["ids"])
         if not self._static:
             self._alloc_static(max(self.cfg.scheduler.max_num_seqs, n))
-        lora = self._lora_batch(None, payload, np_=0)
+        route = self._lora_route(None, payload, np_=0)
+        slot_form = route is not None and route[0] == "slots"
         bucket = next((b for b in _DECODE_BUCKETS if b >= n), None)
+        # base-only steps replay _graphs, slot-form LoRA steps replay
+        # _lora_graphs; torch-loop LoRA steps run eager
+        graphs = (self._graphs if route is None
+                  else self._lora_graphs if slot_form else {})
         use_graph = (
-            bucket is not None and bucket in self._graphs and self.is_cuda
-            and lora is None  # LoRA steps run eager
+            bucket is not None and bucket in graphs and self.is_cuda
         )
         bs = bucket if use_graph else n
         self._fill_decode_inputs(payload, bs)
+        lora = None
+        if slot_form:
+            from fusioninfer_amd.lora import LoRABatch
+
+            buf = self._static["lora_slots"]
+            buf[:n].copy_(torch.from_numpy(route[1]), non_blocking=True)
+            if bs > n:
+                buf[n:bs].fill_(-1)
+            lora = LoRABatch(slot_ids=buf[:n], slots=self.lora_slots)
+        elif route is not None:
+            lora = self._lora_batch_from_groups(route[1])
         if use_graph:
-            g, out = self._graphs[bucket]
+            g, out = graphs[bucket]
             g.replay()
+            if slot_form:
+                self.num_lora_graph_replays += 1
             return out[:n]
+        if lora is not None:
+            self.num_lora_eager_steps += 1
         with torch.no_grad():
             return self._decode_forward(n, lora=lora)[:n]
 

@@ -435,4 +435,55 @@ def moe_combine(out, y, pos, w):
     return ref.moe_combine(out, y, pos, w)
 
 
+# ---------------------------------------------------------------- LoRA
+
+LORA_MAX_RANK = 128  # kernel contract: R % 16 == 0 and R <= 128
+
+
+def lora_shapes_supported(K: int, N: int, R: int) -> bool:
+    """Shapes the HIP lora_apply kernels cover (any T >= 1)."""
+    return (K % 64 == 0 and N % 16 == 0 and R % 16 == 0
+            and 16 <= R <= LORA_MAX_RANK)
+
+
+def lora_apply(out, x, slot_ids, a_stack, b_stack, scales):
+    """Batched multi-LoRA, in place on out:
+
+        out[t] += scales[s] * bf16(x[t] @ a_stack[s].T) @ b_stack[s].T
+
+    with s = slot_ids[t]; an id outside [0, S) (canonically -1) means "no
+    adapter" and leaves the row bit-for-bit untouched. out [T, N] bf16,
+    x [T, K] bf16, slot_ids [T] int32, a_stack [S, R, K] bf16 and
+    b_stack [S, N, R] bf16 (zero-padded beyond each adapter's rank),
+    scales [S] fp32. Static shapes, no host sync: hipGraph-capturable.
+    Unsupported shapes raise ValueError (no silent fallback)."""
+    T, K = x.shape
+    N = out.shape[1]
+    S, R = a_stack.shape[0], a_stack.shape[1]
+    if (out.shape[0] != T or slot_ids.shape != (T,)
+            or a_stack.shape != (S, R, K) or b_stack.shape != (S, N, R)
+            or scales.shape != (S,)):
+        raise ValueError(
+            f"lora_apply: inconsistent shapes out={tuple(out.shape)} "
+            f"x={tuple(x.shape)} slot_ids={tuple(slot_ids.shape)} "
+            f"a_stack={tuple(a_stack.shape)} b_stack={tuple(b_stack.shape)} "
+            f"scales={tuple(scales.shape)}"
+        )
+    if T < 1 or S < 1 or not lora_shapes_supported(K, N, R):
+        raise ValueError(
+            f"lora_apply: unsupported shape T={T} K={K} N={N} R={R} S={S} "
+            "(need T >= 1, K % 64 == 0, N % 16 == 0, R % 16 == 0, "
+            f"R <= {LORA_MAX_RANK})"
+        )
+    if out.is_cuda:
+        _require_native()
+        if not out.is_contiguous():
+            raise ValueError("lora_apply: out must be contiguous")
+        y_ws = torch.empty((T, R), dtype=out.dtype, device=out.device)
+        _C.lora_apply(out, y_ws, x.contiguous(), slot_ids, a_stack, b_stack,
+                      scales)
+        return out
+    return ref.lora_apply(out, x, slot_ids, a_stack, b_stack, scales)
+
+
 compute_cos_sin_cache = ref.compute_cos_sin_cache

@@ -27,6 +27,7 @@ SOURCES = [
     "paged_attention.hip",
     "prefill_attention.hip",
     "moe_gemm.hip",
+    "lora.hip",
 ]
 
 

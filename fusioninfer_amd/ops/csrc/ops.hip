@@ -45,6 +45,9 @@ void launch_moe_router_topk(const float*, float*, int*, int, int, int,
                             bool, hipStream_t);
 void launch_moe_combine(u16*, const u16*, const int*, const float*, int, int,
                         int, hipStream_t);
+void launch_lora_apply(u16*, u16*, const u16*, const int*, const u16*,
+                       const u16*, const float*, int, int, int, int, int,
+                       hipStream_t);
 
 }  // namespace fi
 
@@ -455,6 +458,46 @@ void moe_router_topk(at::Tensor logits, at::Tensor topv, at::Tensor topi,
                              T, E, (int)k, renorm, current_stream());
 }
 
+void lora_apply(at::Tensor out, at::Tensor y_ws, at::Tensor x,
+                at::Tensor slot_ids, at::Tensor a_stack, at::Tensor b_stack,
+                at::Tensor scales) {
+  CHECK_BF16_CUDA(out);
+  CHECK_BF16_CUDA(y_ws);
+  CHECK_BF16_CUDA(x);
+  CHECK_BF16_CUDA(a_stack);
+  CHECK_BF16_CUDA(b_stack);
+  TORCH_CHECK(out.is_contiguous() && y_ws.is_contiguous() &&
+              x.is_contiguous() && a_stack.is_contiguous() &&
+              b_stack.is_contiguous());
+  TORCH_CHECK(slot_ids.is_cuda() && slot_ids.scalar_type() == at::kInt &&
+              slot_ids.is_contiguous());
+  TORCH_CHECK(scales.is_cuda() && scales.scalar_type() == at::kFloat &&
+              scales.is_contiguous());
+  TORCH_CHECK(out.dim() == 2 && x.dim() == 2 && a_stack.dim() == 3 &&
+              b_stack.dim() == 3);
+  const int64_t T = x.size(0);
+  const int64_t K = x.size(1);
+  const int64_t N = out.size(1);
+  const int64_t S = a_stack.size(0);
+  const int64_t R = a_stack.size(1);
+  TORCH_CHECK(T >= 1 && T < (1LL << 31) - 16 && out.size(0) == T &&
+              slot_ids.numel() == T);
+  TORCH_CHECK(K % 64 == 0 && N % 16 == 0 && R % 16 == 0 && R >= 16 &&
+                  R <= 128,
+              "lora_apply: need K % 64 == 0, N % 16 == 0, R % 16 == 0, "
+              "16 <= R <= 128");
+  TORCH_CHECK(a_stack.size(2) == K && b_stack.size(0) == S &&
+              b_stack.size(1) == N && b_stack.size(2) == R &&
+              scales.numel() == S && S >= 1);
+  TORCH_CHECK(y_ws.dim() == 2 && y_ws.size(0) == T && y_ws.size(1) == R);
+  fi::launch_lora_apply(bf16_ptr(out), bf16_ptr(y_ws), bf16_cptr(x),
+                        slot_ids.data_ptr<int>(), bf16_cptr(a_stack),
+                        bf16_cptr(b_stack), scales.data_ptr<float>(),
+                        static_cast<int>(T), static_cast<int>(K),
+                        static_cast<int>(N), static_cast<int>(R),
+                        static_cast<int>(S), current_stream());
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -491,4 +534,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "(vLLM moe_align_block_size analog)");
   m.def("moe_router_topk", &moe_router_topk,
         "fused router tail: softmax + top-k + optional renormalize");
+  m.def("lora_apply", &lora_apply,
+        "batched multi-LoRA shrink + expand indexed by per-token slot ids "
+        "(in-place on out)");
 }

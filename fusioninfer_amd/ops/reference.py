@@ -375,3 +375,23 @@ def moe_gemm_fp8(out, a, a_scales, b_packed, b_scales, sorted_ids,
             acc = torch.nn.functional.silu(g) * u
         out[rows] = acc.to(out.dtype)
     return out
+
+
+def lora_apply(out, x, slot_ids, a_stack, b_stack, scales):
+    """fp32 reference of the batched multi-LoRA apply (in place on out):
+    out[t] += scales[s] * bf16(x[t] @ a_stack[s].T) @ b_stack[s].T with
+    s = slot_ids[t]. The shrink result is rounded to bf16 once (as the
+    HIP kernels and the per-adapter torch loop do); scale and add run in
+    fp32. Rows whose id is outside [0, S) are left untouched."""
+    S = a_stack.shape[0]
+    ids = slot_ids.long()
+    for s in torch.unique(ids).tolist():
+        if s < 0 or s >= S:
+            continue
+        rows = (ids == s).nonzero().flatten()
+        y = (x[rows].float() @ a_stack[s].float().T).to(torch.bfloat16)
+        delta = y.float() @ b_stack[s].float().T
+        out[rows] = (
+            out[rows].float() + float(scales[s]) * delta
+        ).to(out.dtype)
+    return out

@@ -41,7 +41,15 @@ def parse_args(argv=None):
     p.add_argument("--kv-cache-dtype", choices=["auto", "fp8"], default="auto")
     p.add_argument("--swap-space", type=float, default=0.0,
                    help="GiB of CPU swap for preempted sequences (0=recompute)")
-    p.add_argument("--enable-lora", action="store_true")
+    p.add_argument("--enable-lora", action="store_true",
+                   help="allocate the batched multi-LoRA slot table "
+                        "(--max-loras slots of --max-lora-rank): adapters "
+                        "run on the HIP lora_apply kernels and LoRA decode "
+                        "steps replay hipGraphs")
+    p.add_argument("--max-lora-rank", type=int, default=64,
+                   help="slot-table rank (rounded up to 16, at most 128); "
+                        "adapters of higher stored rank stay on the "
+                        "per-adapter torch path")
     p.add_argument("--max-loras", type=int, default=8)
     p.add_argument("--max-cpu-loras", type=int, default=16,
                    help="accepted for reference-surface parity; adapters "
@@ -134,6 +142,8 @@ def build_engine_config(args):
         speculative=speculative,
         max_loras=args.max_loras,
         max_cpu_loras=args.max_cpu_loras,
+        enable_lora=args.enable_lora,
+        max_lora_rank=args.max_lora_rank,
         enforce_eager=args.enforce_eager,
     )
 

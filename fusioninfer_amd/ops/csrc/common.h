@@ -1,6 +1,7 @@
 // Common device helpers for FusionInfer-AMD CDNA4 (gfx950) kernels.
 //
-// Design notes (see /opt/skills/guides/cdna_hip_programming.md):
+// Design notes (see the CDNA HIP programming guide,
+// cdna_hip_programming.md):
 //  * wave64 everywhere; block sizes are multiples of 64.
 //  * bf16 loads are ALWAYS vectorized (short4/short8 reinterpret, G13).
 //  * bf16<->f32 via bit ops (RNE) — matches hardware v_cvt rounding.

@@ -9,16 +9,24 @@
 // (Capability parity: expert serving the reference invokes via vLLM
 // images; reference publishes no kernels of its own.)
 //
-// Design (per /opt/skills/guides/cdna_hip_programming.md):
-//  * mfma_f32_16x16x32_bf16 per-wave tiles; expert weights are packed
-//    OFFLINE into MFMA B-fragment order [E][K/32][N/16][64][8] so each
-//    wave's per-K-step B load is ONE fully-coalesced 16 B/lane
-//    global_load_dwordx4 (1 KiB per wave per fragment).
-//  * No LDS, no barriers: weights stream once (the decode regime is
-//    weight-bandwidth-bound: every active expert's panel is read ~once
-//    per step), activations are L2-resident; per the guide's GEMV row,
-//    operands streamed once and not shared across waves go straight to
-//    VGPRs with a deep unroll.
+// Design (per the CDNA HIP programming guide, cdna_hip_programming.md):
+//  * ONE kernel template over an element-traits type: Bf16
+//    (mfma_f32_16x16x32_bf16) and Fp8E4m3 (mfma_f32_16x16x32_fp8_fp8:
+//    A e4m3 with per-row scales from the fused-norm / row quant, B e4m3
+//    with per-expert per-out-channel scales — HALF the weight bytes of
+//    bf16 in the weight-bandwidth-bound decode regime, and no per-expert
+//    host loops: round 1 ran per-expert torch._scaled_mm with .nonzero()
+//    syncs). Dequant happens in the epilogue:
+//    v = acc * a_scale[row] * b_scale[col].
+//  * Per-wave 16x16x32 MFMA tiles; expert weights are packed OFFLINE
+//    into MFMA B-fragment order [E][K/32][N/16][64][8] so each wave's
+//    per-K-step B load is ONE fully-coalesced 8-element/lane load
+//    (bf16: 16 B/lane global_load_dwordx4, 1 KiB per wave per fragment).
+//  * BM=16 variants — no LDS, no barriers: weights stream once (the
+//    decode regime is weight-bandwidth-bound: every active expert's
+//    panel is read ~once per step), activations are L2-resident; per the
+//    guide's GEMV row, operands streamed once and not shared across
+//    waves go straight to VGPRs with a deep unroll.
 //  * GEMM1 fuses the SwiGLU epilogue: each wave accumulates the gate
 //    AND up columns for its 16-column slice and writes silu(g)*u —
 //    the [T, 2I] intermediate never round-trips HBM.
@@ -40,9 +48,32 @@ namespace {
 typedef __attribute__((ext_vector_type(8))) short short8;
 typedef __attribute__((ext_vector_type(4))) float floatx4;
 
-FI_DEV short8 load_b16x8(const u16* p) {
-  return *reinterpret_cast<const short8*>(p);
-}
+// Element traits: storage type, the 8-element per-lane K-step fragment,
+// its load, the MFMA, and whether the epilogue applies dequant scales.
+// Everything else (staging geometry, swizzle) follows from sizeof(T).
+struct Bf16 {
+  using T = u16;
+  using Frag = short8;
+  static constexpr bool kScaled = false;
+  static FI_DEV Frag load(const T* p) {
+    return *reinterpret_cast<const Frag*>(p);
+  }
+  static FI_DEV floatx4 mfma(Frag a, Frag b, floatx4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+  }
+};
+
+struct Fp8E4m3 {
+  using T = unsigned char;
+  using Frag = long long;
+  static constexpr bool kScaled = true;
+  static FI_DEV Frag load(const T* p) {
+    return *reinterpret_cast<const Frag*>(p);
+  }
+  static FI_DEV floatx4 mfma(Frag a, Frag b, floatx4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(a, b, c, 0, 0, 0);
+  }
+};
 
 // WM x WN waves (4 total), MITER 16-row fragments per wave, NITER
 // 16-col fragments per wave. Block tile: rows BM = 16*WM*MITER, cols
@@ -58,16 +89,24 @@ FI_DEV short8 load_b16x8(const u16* p) {
 // per K-step — the guide's 2-phase grouped-GEMM shape), so the four
 // waves share one gather of the 128x32 panel instead of issuing
 // per-wave fragment loads against L2/L3.
-template <int WM, int WN, int MITER, int NITER, bool GATE_UP,
-          bool STAGE_A = false>
+// a_scales / b_scales are read only when Elem::kScaled (Bf16 passes
+// null).
+template <class Elem, int WM, int WN, int MITER, int NITER, bool GATE_UP,
+          bool STAGE_A>
 __global__ __launch_bounds__(256) void moe_gemm_kernel(
     u16* __restrict__ out,              // [PM, N] bf16
-    const u16* __restrict__ a,          // GATE_UP: x [T, K]; else act [PM, K]
-    const u16* __restrict__ b,          // [E][K/32][NB/16][64][8] bf16
+    const typename Elem::T* __restrict__ a,  // GATE_UP: x [T, K]; else
+                                             // act [PM, K]
+    const typename Elem::T* __restrict__ b,  // [E][K/32][NB/16][64][8]
     const int* __restrict__ sorted_ids, // [PM] token row per padded slot
     const int* __restrict__ expert_ids, // [PM/BM] local expert per m-tile
     const int* __restrict__ n_valid,    // device scalar: real m-tile count
-    const int K, const int N) {
+    const int K, const int N,
+    const float* __restrict__ a_scales, // [T] / [PM] per-row
+    const float* __restrict__ b_scales) { // [E][NB] per out channel
+  using T = typename Elem::T;
+  using Frag = typename Elem::Frag;
+  constexpr int kES = sizeof(T);
   constexpr int BM = 16 * WM * MITER;
   static_assert(!STAGE_A || BM == 128, "STAGE_A is tuned for BM=128");
   const int mtile = blockIdx.x;
@@ -83,11 +122,10 @@ __global__ __launch_bounds__(256) void moe_gemm_kernel(
   const int row0 = mtile * BM + wm * (16 * MITER);
 
   const int NB16 = (GATE_UP ? 2 * N : N) / 16;  // packed B n-fragments
-  const u16* b_e =
-      b + static_cast<int64_t>(e) * (K / 32) * NB16 * (64 * 8);
+  const T* b_e = b + static_cast<int64_t>(e) * (K / 32) * NB16 * (64 * 8);
   // per-K-step fragment pointers (advance by NB16*512 elements per kt)
-  const u16* bg_p[NITER];
-  const u16* bu_p[NITER];
+  const T* bg_p[NITER];
+  const T* bu_p[NITER];
 #pragma unroll
   for (int ni = 0; ni < NITER; ++ni) {
     bg_p[ni] = b_e + (static_cast<int64_t>(nt0 + ni) * 64 + lane) * 8;
@@ -99,7 +137,7 @@ __global__ __launch_bounds__(256) void moe_gemm_kernel(
 
   // A row pointers: gather through sorted_ids for GEMM1 (padding slots
   // carry a valid dummy row — garbage rows are never read by combine)
-  const u16* a_p[MITER];
+  const T* a_p[MITER];
 #pragma unroll
   for (int mi = 0; mi < MITER; ++mi) {
     const int slot = row0 + mi * 16 + (lane & 15);
@@ -107,39 +145,43 @@ __global__ __launch_bounds__(256) void moe_gemm_kernel(
     a_p[mi] = a + static_cast<int64_t>(row) * K + (lane >> 4) * 8;
   }
 
-  // ---- STAGE_A machinery (BM=128): [128 rows][64 B] tile, rows
-  // swizzled byte^=(row&3)<<4 (T2; glds dest is lane-linear so the
+  // ---- STAGE_A machinery (BM=128): [128 rows][32 elements] tile (64-B
+  // rows for bf16, 32-B rows for e4m3), 16-B pieces swizzled within the
+  // row: byte ^= (row & kSwz) << 4 (T2; glds dest is lane-linear so the
   // swizzle rides on the SOURCE address, rule 21)
-  constexpr int kARowB = 64;                    // 32 bf16 per row
-  constexpr int kATileB = 128 * kARowB;         // 8 KiB
-  __shared__ u16 a_lds[STAGE_A ? 2 * kATileB / 2 : 1];
+  constexpr int kARowB = 32 * kES;              // bytes per staged row
+  constexpr int kATileB = 128 * kARowB;         // 8 KiB bf16 / 4 KiB e4m3
+  constexpr int kATile = kATileB / kES;         // ... in elements
+  constexpr int kSwz = kARowB / 16 - 1;         // 3 bf16 / 1 e4m3
+  constexpr int kPieces = kATileB / 16 / 256;   // 16-B pieces per thread
+  __shared__ alignas(16) T a_lds[STAGE_A ? 2 * kATile : 1];
   const int tid = threadIdx.x;
-  // this thread's two 16-B staging pieces per K-step
-  int stage_src_off[2];   // element offset within the source row
-  int64_t stage_row_off[2];
-  int stage_dst[2];
+  // this thread's 16-B staging pieces per K-step (element offsets)
+  int stage_src_off[kPieces];   // within the source row
+  int64_t stage_row_off[kPieces];
+  int stage_dst[kPieces];
   if (STAGE_A) {
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
+    for (int i = 0; i < kPieces; ++i) {
       const int X = (i * 256 + tid) * 16;       // linear LDS byte
       const int srow = X / kARowB;
-      const int sbyte = (X % kARowB) ^ ((srow & 3) << 4);
+      const int sbyte = (X % kARowB) ^ ((srow & kSwz) << 4);
       const int gr = GATE_UP ? sorted_ids[mtile * BM + srow]
                              : mtile * BM + srow;
       stage_row_off[i] = static_cast<int64_t>(gr) * K;
-      stage_src_off[i] = sbyte / 2;
-      stage_dst[i] = X / 2;
+      stage_src_off[i] = sbyte / kES;
+      stage_dst[i] = X / kES;
     }
   }
   auto stage_a = [&](int kt, int buf) {
     if (!STAGE_A) return;
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const u16* src = a + stage_row_off[i] + kt * 32 + stage_src_off[i];
+    for (int i = 0; i < kPieces; ++i) {
+      const T* src = a + stage_row_off[i] + kt * 32 + stage_src_off[i];
       __builtin_amdgcn_global_load_lds(
           (const __attribute__((address_space(1))) void*)src,
           (__attribute__((address_space(3))) void*)(
-              a_lds + buf * (kATileB / 2) + stage_dst[i]),
+              a_lds + buf * kATile + stage_dst[i]),
           16, 0, 0);
     }
   };
@@ -149,8 +191,8 @@ __global__ __launch_bounds__(256) void moe_gemm_kernel(
 #pragma unroll
     for (int mi = 0; mi < MITER; ++mi) {
       const int srow = wm * (16 * MITER) + mi * 16 + (lane & 15);
-      const int byte = ((lane >> 4) * 16) ^ ((srow & 3) << 4);
-      a_lds_off[mi] = (srow * kARowB + byte) / 2;
+      const int byte = ((lane >> 4) * 8 * kES) ^ ((srow & kSwz) << 4);
+      a_lds_off[mi] = (srow * kARowB + byte) / kES;
     }
     stage_a(0, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -171,23 +213,20 @@ __global__ __launch_bounds__(256) void moe_gemm_kernel(
   if (STAGE_A) {
     for (int kt = 0; kt < ksteps; ++kt) {
       if (kt + 1 < ksteps) stage_a(kt + 1, (kt + 1) & 1);
-      short8 av[MITER];
-      const u16* abuf = a_lds + (kt & 1) * (kATileB / 2);
+      Frag av[MITER];
+      const T* abuf = a_lds + (kt & 1) * kATile;
 #pragma unroll
       for (int mi = 0; mi < MITER; ++mi)
-        av[mi] = load_b16x8(abuf + a_lds_off[mi]);
+        av[mi] = Elem::load(abuf + a_lds_off[mi]);
 #pragma unroll
       for (int ni = 0; ni < NITER; ++ni) {
-        const short8 bg = load_b16x8(bg_p[ni] + kt * b_step);
-        short8 bu;
-        if (GATE_UP) bu = load_b16x8(bu_p[ni] + kt * b_step);
+        const Frag bg = Elem::load(bg_p[ni] + kt * b_step);
+        Frag bu = {};
+        if (GATE_UP) bu = Elem::load(bu_p[ni] + kt * b_step);
 #pragma unroll
         for (int mi = 0; mi < MITER; ++mi) {
-          acc_g[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              av[mi], bg, acc_g[mi][ni], 0, 0, 0);
-          if (GATE_UP)
-            acc_u[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                av[mi], bu, acc_u[mi][ni], 0, 0, 0);
+          acc_g[mi][ni] = Elem::mfma(av[mi], bg, acc_g[mi][ni]);
+          if (GATE_UP) acc_u[mi][ni] = Elem::mfma(av[mi], bu, acc_u[mi][ni]);
         }
       }
       // 2-phase barrier: drains this step's prefetch glds (next tile
@@ -204,31 +243,29 @@ __global__ __launch_bounds__(256) void moe_gemm_kernel(
     // the buffer index compile-time (runtime-indexed register arrays
     // spill to scratch — guide rule 20).
     constexpr int NU = GATE_UP ? NITER : 1;
-    short8 av0[MITER], av1[MITER];
-    short8 bg0[NITER], bg1[NITER];
-    short8 bu0[NU], bu1[NU];
-    auto issue = [&](short8 (&avd)[MITER], short8 (&bgd)[NITER],
-                     short8 (&bud)[NU], int kt) {
+    Frag av0[MITER], av1[MITER];
+    Frag bg0[NITER], bg1[NITER];
+    Frag bu0[NU], bu1[NU];
+    auto issue = [&](Frag (&avd)[MITER], Frag (&bgd)[NITER],
+                     Frag (&bud)[NU], int kt) {
 #pragma unroll
       for (int mi = 0; mi < MITER; ++mi)
-        avd[mi] = load_b16x8(a_p[mi] + kt * 32);
+        avd[mi] = Elem::load(a_p[mi] + kt * 32);
 #pragma unroll
       for (int ni = 0; ni < NITER; ++ni) {
-        bgd[ni] = load_b16x8(bg_p[ni] + kt * b_step);
-        if (GATE_UP) bud[ni] = load_b16x8(bu_p[ni] + kt * b_step);
+        bgd[ni] = Elem::load(bg_p[ni] + kt * b_step);
+        if (GATE_UP) bud[ni] = Elem::load(bu_p[ni] + kt * b_step);
       }
     };
-    auto consume = [&](short8 (&avv)[MITER], short8 (&bgv)[NITER],
-                       short8 (&buv)[NU]) {
+    auto consume = [&](Frag (&avv)[MITER], Frag (&bgv)[NITER],
+                       Frag (&buv)[NU]) {
 #pragma unroll
       for (int ni = 0; ni < NITER; ++ni)
 #pragma unroll
         for (int mi = 0; mi < MITER; ++mi) {
-          acc_g[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              avv[mi], bgv[ni], acc_g[mi][ni], 0, 0, 0);
+          acc_g[mi][ni] = Elem::mfma(avv[mi], bgv[ni], acc_g[mi][ni]);
           if (GATE_UP)
-            acc_u[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                avv[mi], buv[ni % NU], acc_u[mi][ni], 0, 0, 0);
+            acc_u[mi][ni] = Elem::mfma(avv[mi], buv[ni % NU], acc_u[mi][ni]);
         }
     };
     issue(av0, bg0, bu0, 0);
@@ -245,224 +282,26 @@ __global__ __launch_bounds__(256) void moe_gemm_kernel(
 #pragma unroll
   for (int ni = 0; ni < NITER; ++ni) {
     const int col = (nt0 + ni) * 16 + (lane & 15);
+    float bs_g = 1.f, bs_u = 1.f;
+    if constexpr (Elem::kScaled) {
+      const float* bs_e = b_scales + static_cast<int64_t>(e) * NB16 * 16;
+      bs_g = bs_e[col];
+      if (GATE_UP) bs_u = bs_e[N + col];
+    }
 #pragma unroll
     for (int mi = 0; mi < MITER; ++mi) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int orow = row0 + mi * 16 + (lane >> 4) * 4 + r;
-        float v;
-        if (GATE_UP) {
-          const float g = acc_g[mi][ni][r];
-          const float u = acc_u[mi][ni][r];
-          v = (g / (1.f + __expf(-g))) * u;
-        } else {
-          v = acc_g[mi][ni][r];
+        float g = acc_g[mi][ni][r];
+        float u = GATE_UP ? acc_u[mi][ni][r] : 0.f;
+        if constexpr (Elem::kScaled) {
+          const float as = a_scales[GATE_UP ? sorted_ids[orow] : orow];
+          g = g * as * bs_g;
+          u = u * as * bs_u;
         }
+        const float v = GATE_UP ? (g / (1.f + __expf(-g))) * u : g;
         out[static_cast<int64_t>(orow) * N + col] = f32_to_bf16(v);
-      }
-    }
-  }
-}
-
-// fp8 grouped GEMM: A (e4m3, per-row scales from the fused-norm / row
-// quant) x B (e4m3, per-expert per-out-channel scales) on
-// mfma_f32_16x16x32_fp8_fp8 — HALF the weight bytes of bf16 in the
-// weight-bandwidth-bound decode regime, and no per-expert host loops:
-// the fp8 MoE path becomes hipGraph-capturable (round 1 ran per-expert
-// torch._scaled_mm with .nonzero() syncs). Same block-aligned layout
-// and epilogue structure as the bf16 kernel; dequant happens in the
-// epilogue: v = acc * a_scale[row] * b_scale[col].
-typedef long long i64;
-
-template <int WM, int WN, int MITER, int NITER, bool GATE_UP,
-          bool STAGE_A = false>
-__global__ __launch_bounds__(256) void moe_gemm_fp8_kernel(
-    u16* __restrict__ out,               // [PM, N] bf16
-    const unsigned char* __restrict__ a, // e4m3 [T, K] or act8 [PM, K]
-    const float* __restrict__ a_scales,  // [T] / [PM] per-row
-    const unsigned char* __restrict__ b, // [E][K/32][NB/16][64][8] e4m3
-    const float* __restrict__ b_scales,  // [E][NB] per out channel
-    const int* __restrict__ sorted_ids,
-    const int* __restrict__ expert_ids,
-    const int* __restrict__ n_valid,
-    const int K, const int N) {
-  constexpr int BM = 16 * WM * MITER;
-  static_assert(!STAGE_A || BM == 128, "STAGE_A is tuned for BM=128");
-  const int mtile = blockIdx.x;
-  if (mtile >= *n_valid) return;
-
-  const int lane = threadIdx.x % kWaveSize;
-  const int wave = threadIdx.x / kWaveSize;
-  const int wm = wave / WN;
-  const int wn = wave % WN;
-  const int nt0 = (blockIdx.y * WN + wn) * NITER;
-  const int e = expert_ids[mtile];
-  const int row0 = mtile * BM + wm * (16 * MITER);
-
-  const int NB16 = (GATE_UP ? 2 * N : N) / 16;
-  const unsigned char* b_e =
-      b + static_cast<int64_t>(e) * (K / 32) * NB16 * (64 * 8);
-  const float* bs_e = b_scales + static_cast<int64_t>(e) * NB16 * 16;
-  const unsigned char* bg_p[NITER];
-  const unsigned char* bu_p[NITER];
-#pragma unroll
-  for (int ni = 0; ni < NITER; ++ni) {
-    bg_p[ni] = b_e + (static_cast<int64_t>(nt0 + ni) * 64 + lane) * 8;
-    bu_p[ni] = GATE_UP
-        ? b_e + ((static_cast<int64_t>(nt0 + ni) + N / 16) * 64 + lane) * 8
-        : nullptr;
-  }
-  const int64_t b_step = static_cast<int64_t>(NB16) * 64 * 8;
-
-  const unsigned char* a_p[MITER];
-  int a_row[MITER];
-#pragma unroll
-  for (int mi = 0; mi < MITER; ++mi) {
-    const int slot = row0 + mi * 16 + (lane & 15);
-    a_row[mi] = GATE_UP ? sorted_ids[slot] : slot;
-    a_p[mi] = a + static_cast<int64_t>(a_row[mi]) * K + (lane >> 4) * 8;
-  }
-
-  // STAGE_A (BM=128): [128 rows][32 B] e4m3 tile through LDS via glds
-  // (2-phase; swizzle byte^=(row&1)<<4 on the SOURCE — rule 21)
-  constexpr int kARowB = 32;                    // 32 e4m3 per row
-  constexpr int kATileB = 128 * kARowB;         // 4 KiB
-  __shared__ unsigned char a8_lds[STAGE_A ? 2 * kATileB : 1];
-  const int tid = threadIdx.x;
-  int64_t stage_row_off = 0;
-  int stage_src_off = 0, stage_dst = 0;
-  if (STAGE_A) {
-    const int X = tid * 16;                     // one 16-B piece per thread
-    const int srow = X / kARowB;
-    const int sbyte = (X % kARowB) ^ ((srow & 1) << 4);
-    const int gr = GATE_UP ? sorted_ids[mtile * BM + srow]
-                           : mtile * BM + srow;
-    stage_row_off = static_cast<int64_t>(gr) * K;
-    stage_src_off = sbyte;
-    stage_dst = X;
-  }
-  auto stage_a = [&](int kt, int buf) {
-    if (!STAGE_A) return;
-    const unsigned char* src = a + stage_row_off + kt * 32 + stage_src_off;
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) void*)src,
-        (__attribute__((address_space(3))) void*)(
-            a8_lds + buf * kATileB + stage_dst),
-        16, 0, 0);
-  };
-  int a_lds_off[MITER];
-  if (STAGE_A) {
-#pragma unroll
-    for (int mi = 0; mi < MITER; ++mi) {
-      const int srow = wm * (16 * MITER) + mi * 16 + (lane & 15);
-      const int byte = ((lane >> 4) * 8) ^ ((srow & 1) << 4);
-      a_lds_off[mi] = srow * kARowB + byte;
-    }
-    stage_a(0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-  }
-
-  floatx4 acc_g[MITER][NITER];
-  floatx4 acc_u[GATE_UP ? MITER : 1][NITER];
-#pragma unroll
-  for (int mi = 0; mi < MITER; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < NITER; ++ni) {
-      acc_g[mi][ni] = {0.f, 0.f, 0.f, 0.f};
-      if (GATE_UP) acc_u[mi][ni] = {0.f, 0.f, 0.f, 0.f};
-    }
-
-  const int ksteps = K / 32;
-  if (STAGE_A) {
-    for (int kt = 0; kt < ksteps; ++kt) {
-      if (kt + 1 < ksteps) stage_a(kt + 1, (kt + 1) & 1);
-      const unsigned char* abuf = a8_lds + (kt & 1) * kATileB;
-      i64 av[MITER];
-#pragma unroll
-      for (int mi = 0; mi < MITER; ++mi)
-        av[mi] = *reinterpret_cast<const i64*>(abuf + a_lds_off[mi]);
-#pragma unroll
-      for (int ni = 0; ni < NITER; ++ni) {
-        const i64 bg = *reinterpret_cast<const i64*>(bg_p[ni] + kt * b_step);
-        i64 bu = 0;
-        if (GATE_UP)
-          bu = *reinterpret_cast<const i64*>(bu_p[ni] + kt * b_step);
-#pragma unroll
-        for (int mi = 0; mi < MITER; ++mi) {
-          acc_g[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(
-              av[mi], bg, acc_g[mi][ni], 0, 0, 0);
-          if (GATE_UP)
-            acc_u[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(
-                av[mi], bu, acc_u[mi][ni], 0, 0, 0);
-        }
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-    }
-  } else {
-    // register double-buffered pipeline (see the bf16 kernel: the
-    // BM=16 decode variants are latency-bound without it; unroll-by-2
-    // keeps buffer indices compile-time — rule 20)
-    constexpr int NU = GATE_UP ? NITER : 1;
-    i64 av0[MITER], av1[MITER], bg0[NITER], bg1[NITER], bu0[NU], bu1[NU];
-    auto issue = [&](i64 (&avd)[MITER], i64 (&bgd)[NITER],
-                     i64 (&bud)[NU], int kt) {
-#pragma unroll
-      for (int mi = 0; mi < MITER; ++mi)
-        avd[mi] = *reinterpret_cast<const i64*>(a_p[mi] + kt * 32);
-#pragma unroll
-      for (int ni = 0; ni < NITER; ++ni) {
-        bgd[ni] = *reinterpret_cast<const i64*>(bg_p[ni] + kt * b_step);
-        if (GATE_UP)
-          bud[ni] = *reinterpret_cast<const i64*>(bu_p[ni] + kt * b_step);
-      }
-    };
-    auto consume = [&](i64 (&avv)[MITER], i64 (&bgv)[NITER],
-                       i64 (&buv)[NU]) {
-#pragma unroll
-      for (int ni = 0; ni < NITER; ++ni)
-#pragma unroll
-        for (int mi = 0; mi < MITER; ++mi) {
-          acc_g[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(
-              avv[mi], bgv[ni], acc_g[mi][ni], 0, 0, 0);
-          if (GATE_UP)
-            acc_u[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(
-                avv[mi], buv[ni % NU], acc_u[mi][ni], 0, 0, 0);
-        }
-    };
-    issue(av0, bg0, bu0, 0);
-    for (int kt = 0; kt < ksteps; kt += 2) {
-      if (kt + 1 < ksteps) issue(av1, bg1, bu1, kt + 1);
-      consume(av0, bg0, bu0);
-      if (kt + 1 < ksteps) {
-        if (kt + 2 < ksteps) issue(av0, bg0, bu0, kt + 2);
-        consume(av1, bg1, bu1);
-      }
-    }
-  }
-
-#pragma unroll
-  for (int ni = 0; ni < NITER; ++ni) {
-    const int col = (nt0 + ni) * 16 + (lane & 15);
-    const float bs_g = bs_e[col];
-    const float bs_u = GATE_UP ? bs_e[N + col] : 0.f;
-#pragma unroll
-    for (int mi = 0; mi < MITER; ++mi) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int oslot = row0 + mi * 16 + (lane >> 4) * 4 + r;
-        const int arow = GATE_UP ? sorted_ids[oslot] : oslot;
-        const float as = a_scales[arow];
-        float v;
-        if (GATE_UP) {
-          const float g = acc_g[mi][ni][r] * as * bs_g;
-          const float u = acc_u[mi][ni][r] * as * bs_u;
-          v = (g / (1.f + __expf(-g))) * u;
-        } else {
-          v = acc_g[mi][ni][r] * as * bs_g;
-        }
-        out[static_cast<int64_t>(oslot) * N + col] = f32_to_bf16(v);
       }
     }
   }
@@ -497,53 +336,52 @@ __global__ void moe_combine_kernel(u16* __restrict__ out,
 
 }  // namespace
 
+// FI_MOE_STAGE_A=0 falls back to the register-gather form of the BM=128
+// variants (A/B knob; read once per process)
+static bool moe_stage_a() {
+  static const bool on = [] {
+    const char* e = getenv("FI_MOE_STAGE_A");
+    return !(e && e[0] == '0');
+  }();
+  return on;
+}
+
 // block_m 16: decode regime (few rows per expert; WM=1,WN=4,MITER=1 —
 // weight-streaming-bound, A is tiny/L2-resident).
 // block_m 128: prefill regime (WM=2,WN=2,MITER=4) with NITER 2 (gate_up,
 // BN=64) / 4 (down, BN=128) so the block's A-panel read amortizes over
 // 4x the output columns of v1.
+template <class Elem>
+static void launch_moe_gemm_impl(
+    u16* out, const typename Elem::T* a, const typename Elem::T* b,
+    const float* a_scales, const float* b_scales, const int* sorted_ids,
+    const int* expert_ids, const int* n_valid, int max_mtiles, int K, int N,
+    int block_m, bool gate_up, hipStream_t stream) {
+  decltype(&moe_gemm_kernel<Elem, 1, 4, 1, 1, true, false>) kernel;
+  int bn = 64;
+  if (block_m == 16) {
+    kernel = gate_up ? moe_gemm_kernel<Elem, 1, 4, 1, 1, true, false>
+                     : moe_gemm_kernel<Elem, 1, 4, 1, 1, false, false>;
+  } else if (gate_up) {  // block_m == 128
+    kernel = moe_stage_a() ? moe_gemm_kernel<Elem, 2, 2, 4, 2, true, true>
+                           : moe_gemm_kernel<Elem, 2, 2, 4, 2, true, false>;
+  } else {
+    bn = 128;
+    kernel = moe_stage_a() ? moe_gemm_kernel<Elem, 2, 2, 4, 4, false, true>
+                           : moe_gemm_kernel<Elem, 2, 2, 4, 4, false, false>;
+  }
+  hipLaunchKernelGGL(kernel, dim3(max_mtiles, N / bn), dim3(256), 0, stream,
+                     out, a, b, sorted_ids, expert_ids, n_valid, K, N,
+                     a_scales, b_scales);
+}
+
 void launch_moe_gemm(u16* out, const u16* a, const u16* b,
                      const int* sorted_ids, const int* expert_ids,
                      const int* n_valid, int max_mtiles, int K, int N,
                      int block_m, bool gate_up, hipStream_t stream) {
-  if (block_m == 16) {
-    const dim3 grid(max_mtiles, N / 64);
-    if (gate_up)
-      hipLaunchKernelGGL((moe_gemm_kernel<1, 4, 1, 1, true>), grid, dim3(256),
-                         0, stream, out, a, b, sorted_ids, expert_ids,
-                         n_valid, K, N);
-    else
-      hipLaunchKernelGGL((moe_gemm_kernel<1, 4, 1, 1, false>), grid,
-                         dim3(256), 0, stream, out, a, b, sorted_ids,
-                         expert_ids, n_valid, K, N);
-  } else {  // block_m == 128
-    // FI_MOE_STAGE_A=0 falls back to the register-gather form (A/B knob)
-    static const bool stage_a = [] {
-      const char* e = getenv("FI_MOE_STAGE_A");
-      return !(e && e[0] == '0');
-    }();
-    if (gate_up) {
-      const dim3 grid(max_mtiles, N / 64);
-      if (stage_a)
-        hipLaunchKernelGGL((moe_gemm_kernel<2, 2, 4, 2, true, true>), grid,
-                           dim3(256), 0, stream, out, a, b, sorted_ids,
-                           expert_ids, n_valid, K, N);
-      else
-        hipLaunchKernelGGL((moe_gemm_kernel<2, 2, 4, 2, true, false>), grid,
-                           dim3(256), 0, stream, out, a, b, sorted_ids,
-                           expert_ids, n_valid, K, N);
-    } else {
-      const dim3 grid(max_mtiles, N / 128);
-      if (stage_a)
-        hipLaunchKernelGGL((moe_gemm_kernel<2, 2, 4, 4, false, true>), grid,
-                           dim3(256), 0, stream, out, a, b, sorted_ids,
-                           expert_ids, n_valid, K, N);
-      else
-        hipLaunchKernelGGL((moe_gemm_kernel<2, 2, 4, 4, false, false>), grid,
-                           dim3(256), 0, stream, out, a, b, sorted_ids,
-                           expert_ids, n_valid, K, N);
-    }
-  }
+  launch_moe_gemm_impl<Bf16>(out, a, b, nullptr, nullptr, sorted_ids,
+                             expert_ids, n_valid, max_mtiles, K, N, block_m,
+                             gate_up, stream);
 }
 
 void launch_moe_gemm_fp8(u16* out, const unsigned char* a,
@@ -552,43 +390,9 @@ void launch_moe_gemm_fp8(u16* out, const unsigned char* a,
                          const int* expert_ids, const int* n_valid,
                          int max_mtiles, int K, int N, int block_m,
                          bool gate_up, hipStream_t stream) {
-  if (block_m == 16) {
-    const dim3 grid(max_mtiles, N / 64);
-    if (gate_up)
-      hipLaunchKernelGGL((moe_gemm_fp8_kernel<1, 4, 1, 1, true>), grid,
-                         dim3(256), 0, stream, out, a, a_scales, b, b_scales,
-                         sorted_ids, expert_ids, n_valid, K, N);
-    else
-      hipLaunchKernelGGL((moe_gemm_fp8_kernel<1, 4, 1, 1, false>), grid,
-                         dim3(256), 0, stream, out, a, a_scales, b, b_scales,
-                         sorted_ids, expert_ids, n_valid, K, N);
-  } else {
-    static const bool stage_a8 = [] {
-      const char* e = getenv("FI_MOE_STAGE_A");
-      return !(e && e[0] == '0');
-    }();
-    if (gate_up) {
-      const dim3 grid(max_mtiles, N / 64);
-      if (stage_a8)
-        hipLaunchKernelGGL((moe_gemm_fp8_kernel<2, 2, 4, 2, true, true>),
-                           grid, dim3(256), 0, stream, out, a, a_scales, b,
-                           b_scales, sorted_ids, expert_ids, n_valid, K, N);
-      else
-        hipLaunchKernelGGL((moe_gemm_fp8_kernel<2, 2, 4, 2, true, false>),
-                           grid, dim3(256), 0, stream, out, a, a_scales, b,
-                           b_scales, sorted_ids, expert_ids, n_valid, K, N);
-    } else {
-      const dim3 grid(max_mtiles, N / 128);
-      if (stage_a8)
-        hipLaunchKernelGGL((moe_gemm_fp8_kernel<2, 2, 4, 4, false, true>),
-                           grid, dim3(256), 0, stream, out, a, a_scales, b,
-                           b_scales, sorted_ids, expert_ids, n_valid, K, N);
-      else
-        hipLaunchKernelGGL((moe_gemm_fp8_kernel<2, 2, 4, 4, false, false>),
-                           grid, dim3(256), 0, stream, out, a, a_scales, b,
-                           b_scales, sorted_ids, expert_ids, n_valid, K, N);
-    }
-  }
+  launch_moe_gemm_impl<Fp8E4m3>(out, a, b, a_scales, b_scales, sorted_ids,
+                                expert_ids, n_valid, max_mtiles, K, N,
+                                block_m, gate_up, stream);
 }
 
 void launch_moe_combine(u16* out, const u16* y, const int* pos,

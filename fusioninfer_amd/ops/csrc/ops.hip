@@ -339,14 +339,18 @@ void prefill_attention_paged(at::Tensor out, at::Tensor q, at::Tensor k_cache,
       static_cast<int>(tile_rows / 32), current_stream());
 }
 
-void moe_gemm(at::Tensor out, at::Tensor a, at::Tensor b_packed,
-              at::Tensor sorted_ids, at::Tensor expert_ids,
-              at::Tensor n_valid, int64_t block_m, bool gate_up) {
-  CHECK_BF16_CUDA(out);
-  CHECK_BF16_CUDA(a);
-  CHECK_BF16_CUDA(b_packed);
-  TORCH_CHECK(out.is_contiguous() && a.is_contiguous() &&
-              b_packed.is_contiguous());
+// Shape checks shared by the bf16 and fp8 grouped GEMMs (dtype checks
+// stay with the callers).
+struct MoeGemmDims {
+  int K, N, max_mtiles;
+};
+
+MoeGemmDims check_moe_gemm(const at::Tensor& out, const at::Tensor& a,
+                           const at::Tensor& b_packed,
+                           const at::Tensor& sorted_ids,
+                           const at::Tensor& expert_ids,
+                           const at::Tensor& n_valid, int64_t block_m,
+                           bool gate_up) {
   TORCH_CHECK(sorted_ids.scalar_type() == at::kInt &&
               expert_ids.scalar_type() == at::kInt &&
               n_valid.scalar_type() == at::kInt);
@@ -366,11 +370,24 @@ void moe_gemm(at::Tensor out, at::Tensor a, at::Tensor b_packed,
               "b_packed layout mismatch");
   TORCH_CHECK(expert_ids.size(0) >= PM / block_m);
   if (gate_up) TORCH_CHECK(sorted_ids.size(0) >= PM);
+  return {K, N, static_cast<int>(PM / block_m)};
+}
+
+void moe_gemm(at::Tensor out, at::Tensor a, at::Tensor b_packed,
+              at::Tensor sorted_ids, at::Tensor expert_ids,
+              at::Tensor n_valid, int64_t block_m, bool gate_up) {
+  CHECK_BF16_CUDA(out);
+  CHECK_BF16_CUDA(a);
+  CHECK_BF16_CUDA(b_packed);
+  TORCH_CHECK(out.is_contiguous() && a.is_contiguous() &&
+              b_packed.is_contiguous());
+  const MoeGemmDims d = check_moe_gemm(out, a, b_packed, sorted_ids,
+                                       expert_ids, n_valid, block_m, gate_up);
   fi::launch_moe_gemm(bf16_ptr(out), bf16_cptr(a),
                       bf16_cptr(b_packed), sorted_ids.data_ptr<int>(),
                       expert_ids.data_ptr<int>(), n_valid.data_ptr<int>(),
-                      PM / block_m, K, N, static_cast<int>(block_m), gate_up,
-                      current_stream());
+                      d.max_mtiles, d.K, d.N, static_cast<int>(block_m),
+                      gate_up, current_stream());
 }
 
 void moe_gemm_fp8(at::Tensor out, at::Tensor a, at::Tensor a_scales,
@@ -385,27 +402,17 @@ void moe_gemm_fp8(at::Tensor out, at::Tensor a, at::Tensor a_scales,
   TORCH_CHECK(a_scales.scalar_type() == at::kFloat &&
               b_scales.scalar_type() == at::kFloat &&
               b_scales.is_contiguous());
-  TORCH_CHECK(sorted_ids.scalar_type() == at::kInt &&
-              expert_ids.scalar_type() == at::kInt &&
-              n_valid.scalar_type() == at::kInt);
-  TORCH_CHECK(block_m == 16 || block_m == 128);
-  const int K = a.size(1);
-  const int N = out.size(1);
-  const int PM = out.size(0);
-  TORCH_CHECK(PM % block_m == 0 && K % 32 == 0);
-  TORCH_CHECK(N % (block_m == 16 ? 64 : (gate_up ? 64 : 128)) == 0);
-  TORCH_CHECK(b_packed.dim() == 5 && b_packed.size(1) == K / 32 &&
-              b_packed.size(2) == (gate_up ? 2 * N : N) / 16 &&
-              b_packed.size(3) == 64 && b_packed.size(4) == 8);
+  const MoeGemmDims d = check_moe_gemm(out, a, b_packed, sorted_ids,
+                                       expert_ids, n_valid, block_m, gate_up);
   TORCH_CHECK(b_scales.numel() ==
-              b_packed.size(0) * (gate_up ? 2 * N : N));
+              b_packed.size(0) * (gate_up ? 2 * d.N : d.N));
   fi::launch_moe_gemm_fp8(
       bf16_ptr(out), static_cast<const unsigned char*>(a.data_ptr()),
       a_scales.data_ptr<float>(),
       static_cast<const unsigned char*>(b_packed.data_ptr()),
       b_scales.data_ptr<float>(), sorted_ids.data_ptr<int>(),
-      expert_ids.data_ptr<int>(), n_valid.data_ptr<int>(), PM / block_m, K,
-      N, static_cast<int>(block_m), gate_up, current_stream());
+      expert_ids.data_ptr<int>(), n_valid.data_ptr<int>(), d.max_mtiles,
+      d.K, d.N, static_cast<int>(block_m), gate_up, current_stream());
 }
 
 void moe_combine(at::Tensor out, at::Tensor y, at::Tensor pos, at::Tensor w) {

@@ -6,6 +6,9 @@ ops/reference.py on random inputs.
 """
 
 import math
+import os
+import subprocess
+import sys
 
 import pytest
 import torch
@@ -429,50 +432,106 @@ def test_kv_block_copy_fp8_roundtrip():
 # ---------------------------------------------------------------- MoE
 
 
-@pytest.mark.parametrize("block_m", [16, 128])
-@pytest.mark.parametrize("gate_up", [True, False])
-def test_moe_gemm_vs_reference(block_m, gate_up):
-    """Grouped MFMA GEMM vs the CPU fp32 reference (same align inputs)."""
-    torch.manual_seed(block_m + int(gate_up))
-    E, K, N = 5, 256, 128
-    T = 300
-    w = torch.randn(E, K, (2 * N) if gate_up else N,
-                    dtype=torch.bfloat16, device=DEV) * 0.05
-    b_packed = ops.pack_moe_weights(w)
-    # synthetic block-aligned assignment: uneven expert loads
+# K-steps of 32: one (prologue only, no prefetch), three (odd: the tail of
+# the unroll-by-2 loop), eight (even)
+MOE_KS = (32, 96, 256)
+
+
+def _check_moe_gemm(fp8, block_m, gate_up, K):
+    """One grouped-GEMM case vs the CPU fp32 reference (same align
+    inputs): uneven expert loads with an empty expert, a partly filled
+    tile and two slack tiles past n_valid; N = 256 puts more than one
+    block on the n axis of every variant (BN is 64 or 128)."""
+    torch.manual_seed(1000 * int(fp8) + K + block_m + int(gate_up))
+    E, N, T = 5, 256, 300
+    NB = (2 * N) if gate_up else N
     counts = [0, 7, block_m, 2 * block_m + 3, 1]
-    tiles = [-(-c // block_m) for c in counts if c > 0]
-    n_tiles = sum(tiles)
+    n_tiles = sum(-(-c // block_m) for c in counts)
     PM = (n_tiles + 2) * block_m  # slack tiles past n_valid stay untouched
-    sorted_ids = torch.zeros(PM, dtype=torch.int32, device=DEV)
-    expert_ids = torch.zeros(PM // block_m, dtype=torch.int32, device=DEV)
-    p = 0
-    t = 0
+    sorted_ids = torch.zeros(PM, dtype=torch.int32)
+    expert_ids = torch.zeros(PM // block_m, dtype=torch.int32)
+    p = t = 0
     for e, c in enumerate(counts):
-        if c == 0:
-            continue
         nt = -(-c // block_m)
-        for i in range(c):
-            sorted_ids[p + i] = t % T
-            t += 3
+        sorted_ids[p : p + c] = (torch.arange(t, t + 3 * c, 3) % T).int()
+        t += 3 * c
         expert_ids[p // block_m : p // block_m + nt] = e
         p += nt * block_m
-    n_valid = torch.tensor([n_tiles], dtype=torch.int32, device=DEV)
-    a = torch.randn(max(T, PM), K, dtype=torch.bfloat16, device=DEV)
+    n_valid = torch.tensor([n_tiles], dtype=torch.int32)
+    ids = [x.to(DEV) for x in (sorted_ids, expert_ids, n_valid)]
     out = torch.full((PM, N), float("nan"), dtype=torch.bfloat16, device=DEV)
-    ops.moe_gemm(out, a, b_packed, sorted_ids, expert_ids, n_valid,
-                 block_m, gate_up)
     want = torch.full((PM, N), float("nan"), dtype=torch.bfloat16)
-    from fusioninfer_amd.ops import reference as _r
-
-    _r.moe_gemm(want, a.cpu(), b_packed.cpu(), sorted_ids.cpu(),
-                expert_ids.cpu(), n_valid.cpu(), block_m, gate_up)
+    if fp8:
+        w = (torch.randn(E, K, NB) * 0.1).to(torch.float8_e4m3fn)
+        ws = torch.rand(E, NB, dtype=torch.float32) * 0.2 + 0.01
+        b_packed = ops.pack_moe_weights(w.view(torch.int8)).view(
+            torch.float8_e4m3fn)
+        a = (torch.randn(max(T, PM), K) * 0.3).to(torch.float8_e4m3fn)
+        a_s = torch.rand(max(T, PM), dtype=torch.float32) + 0.1
+        ops.moe_gemm_fp8(out, a.to(DEV), a_s.to(DEV), b_packed.to(DEV),
+                         ws.to(DEV), *ids, block_m, gate_up)
+        ref.moe_gemm_fp8(want, a, a_s, b_packed, ws, sorted_ids, expert_ids,
+                         n_valid, block_m, gate_up)
+        tol = 5e-2
+    else:
+        w = torch.randn(E, K, NB, dtype=torch.bfloat16) * 0.05
+        b_packed = ops.pack_moe_weights(w)
+        a = torch.randn(max(T, PM), K, dtype=torch.bfloat16)
+        ops.moe_gemm(out, a.to(DEV), b_packed.to(DEV), *ids, block_m,
+                     gate_up)
+        ref.moe_gemm(want, a, b_packed, sorted_ids, expert_ids, n_valid,
+                     block_m, gate_up)
+        tol = 3e-2
     rows = n_tiles * block_m
     torch.testing.assert_close(
-        out[:rows].float().cpu(), want[:rows].float(), atol=3e-2, rtol=3e-2
+        out[:rows].float().cpu(), want[:rows].float(), atol=tol, rtol=tol
     )
     # tiles past n_valid untouched on both
     assert out[rows:].isnan().all()
+    assert want[rows:].isnan().all()
+
+
+@pytest.mark.parametrize("K", MOE_KS)
+@pytest.mark.parametrize("block_m", [16, 128])
+@pytest.mark.parametrize("gate_up", [True, False])
+def test_moe_gemm_vs_reference(block_m, gate_up, K):
+    """Grouped MFMA GEMM vs the CPU fp32 reference (same align inputs)."""
+    _check_moe_gemm(False, block_m, gate_up, K)
+
+
+@pytest.mark.parametrize("K", MOE_KS)
+@pytest.mark.parametrize("block_m", [16, 128])
+@pytest.mark.parametrize("gate_up", [True, False])
+def test_moe_gemm_fp8_vs_reference(block_m, gate_up, K):
+    """Grouped fp8 GEMM (dequant epilogue) vs the CPU fp32 reference."""
+    _check_moe_gemm(True, block_m, gate_up, K)
+
+
+_REGISTER_GATHER_CHILD = """
+import sys
+sys.path.insert(0, sys.argv[1])
+import test_ops_gpu as t
+t.setup_module()
+for fp8 in (False, True):
+    for gate_up in (True, False):
+        for K in t.MOE_KS:
+            t._check_moe_gemm(fp8, 128, gate_up, K)
+"""
+
+
+def test_moe_gemm_register_gather_variants():
+    """FI_MOE_STAGE_A=0 selects the BM=128 variants that gather A into
+    registers instead of staging it through LDS. The knob is read once
+    per process, so the block_m=128 cases of both dtypes run in one
+    child; any mismatch there raises and the child exits non-zero."""
+    tests_dir = os.path.dirname(os.path.abspath(__file__))
+    child = subprocess.run(
+        [sys.executable, "-c", _REGISTER_GATHER_CHILD, tests_dir],
+        env={**os.environ, "FI_MOE_STAGE_A": "0"},
+        cwd=os.path.dirname(tests_dir), capture_output=True, text=True,
+        timeout=300,
+    )
+    assert child.returncode == 0, child.stderr[-2000:]
 
 
 def test_moe_combine_vs_reference():
@@ -519,52 +578,6 @@ def test_moe_grouped_forward_matches_manual():
                 exp[t] += float(topv[t, k]) * y
         rel = (got - exp).norm() / exp.norm()
         assert rel.item() < 0.05, (T, rel.item())
-
-
-def test_moe_gemm_fp8_vs_reference():
-    """Grouped fp8 GEMM (dequant epilogue) vs the CPU fp32 reference."""
-    torch.manual_seed(9)
-    E, K, N, T = 4, 128, 128, 200
-    for gate_up in (True, False):
-        w = (torch.randn(E, K, (2 * N) if gate_up else N) * 0.1).to(
-            torch.float8_e4m3fn).cuda()
-        ws = torch.rand(E, (2 * N) if gate_up else N,
-                        dtype=torch.float32, device=DEV) * 0.2 + 0.01
-        b_packed = ops.pack_moe_weights(w.view(torch.int8)).view(
-            torch.float8_e4m3fn)
-        block_m = 16
-        counts = [5, 0, 2 * block_m, 9]
-        tiles = [-(-c // block_m) for c in counts if c > 0]
-        n_tiles = sum(tiles)
-        PM = (n_tiles + 1) * block_m
-        sorted_ids = torch.zeros(PM, dtype=torch.int32, device=DEV)
-        expert_ids = torch.zeros(PM // block_m, dtype=torch.int32, device=DEV)
-        p = t = 0
-        for e, c in enumerate(counts):
-            if c == 0:
-                continue
-            nt = -(-c // block_m)
-            for i in range(c):
-                sorted_ids[p + i] = t % T
-                t += 7
-            expert_ids[p // block_m: p // block_m + nt] = e
-            p += nt * block_m
-        n_valid = torch.tensor([n_tiles], dtype=torch.int32, device=DEV)
-        a = (torch.randn(max(T, PM), K) * 0.3).to(torch.float8_e4m3fn).cuda()
-        a_s = torch.rand(max(T, PM), dtype=torch.float32, device=DEV) + 0.1
-        out = torch.zeros(PM, N, dtype=torch.bfloat16, device=DEV)
-        ops.moe_gemm_fp8(out, a, a_s, b_packed, ws, sorted_ids, expert_ids,
-                         n_valid, block_m, gate_up)
-        want = torch.zeros(PM, N, dtype=torch.bfloat16)
-        from fusioninfer_amd.ops import reference as _r
-
-        _r.moe_gemm_fp8(want, a.cpu(), a_s.cpu(), b_packed.cpu(), ws.cpu(),
-                        sorted_ids.cpu(), expert_ids.cpu(), n_valid.cpu(),
-                        block_m, gate_up)
-        rows = n_tiles * block_m
-        torch.testing.assert_close(out[:rows].float().cpu(),
-                                   want[:rows].float(),
-                                   atol=5e-2, rtol=5e-2)
 
 
 def test_moe_align_kernel_matches_python():

@@ -147,4 +147,8 @@ class EngineConfig:
     enable_lora: bool = False
     max_lora_rank: int = 64
     seed: int = 0
+    # "torch": the PyTorch sampler. "fused": one HIP sample_tokens launch
+    # per step (counter-based seeded draws, keeps seeded requests on the
+    # pipelined-decode chain).
+    sampler_backend: str = "torch"
     enforce_eager: bool = False            # True disables hipGraph decode capture

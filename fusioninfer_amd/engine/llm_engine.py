@@ -85,7 +85,8 @@ class LLMEngine:
                 and cfg.parallel.tensor_parallel_size == 1
                 and cfg.parallel.pipeline_parallel_size == 1):
             self.scheduler.swap_out_fn = self._swap_out
-        self.sampler = Sampler(cfg.seed, device)
+        self.sampler = Sampler(cfg.seed, device,
+                               backend=cfg.sampler_backend)
         from fusioninfer_amd.engine.spec_decode import build_proposer
 
         if (cfg.speculative is not None
@@ -659,8 +660,7 @@ class LLMEngine:
         return RequestOutput(seq, new_token_ids=new)
 
     # ------------------------------------------------- pipelined decode
-    @staticmethod
-    def _seq_async_ok(s: Sequence) -> bool:
+    def _seq_async_ok(self, s: Sequence) -> bool:
         """Pipeline-eligible: nothing about next-step sampling may depend
         on THIS step's token value on the host (guided masks, penalties
         over emitted tokens) and nothing extra is read back (logprobs)."""
@@ -674,8 +674,12 @@ class LLMEngine:
             and sp.presence_penalty == 0.0
             and sp.frequency_penalty == 0.0
             and s.lora_name is None
-            # seeded draws key on len(output) — one short pre-drain
-            and (sp.temperature == 0 or sp.seed is None)
+            # torch backend: seeded draws key on len(output) — one short
+            # pre-drain. The fused backend's (seed, len(output)) offset is
+            # a host-known integer and _drain_pending runs before the next
+            # _stash_pending, so seeded rows stay eligible there.
+            and (sp.temperature == 0 or sp.seed is None
+                 or self.sampler.backend == "fused")
         )
 
     def _stash_pending(self, seqs, logits) -> None:

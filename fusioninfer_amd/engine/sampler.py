@@ -11,10 +11,30 @@ import torch
 from fusioninfer_amd.engine.sequence import Sequence
 
 
+BACKENDS = ("torch", "fused")
+
+# unseeded draws of the fused backend take Philox offsets from here up;
+# seeded requests use len(output_token_ids), far below
+_UNSEEDED_OFFSET_BASE = 1 << 62
+
+
+def _as_i64(v: int) -> int:
+    """Wrap an arbitrary Python int into the int64 range (bit pattern kept)."""
+    v &= (1 << 64) - 1
+    return v - (1 << 64) if v >= (1 << 63) else v
+
+
 class Sampler:
-    def __init__(self, seed: int = 0, device: str = "cpu"):
+    def __init__(self, seed: int = 0, device: str = "cpu",
+                 backend: str = "torch"):
+        if backend not in BACKENDS:
+            raise ValueError(
+                f"sampler backend must be one of {BACKENDS}, got {backend!r}"
+            )
         self.device = device
         self.base_seed = seed
+        self.backend = backend
+        self.num_unseeded_draws = 0  # fused backend: running Philox offset
         self.generator = None
         if device != "cpu":
             self.generator = torch.Generator(device=device)
@@ -52,6 +72,8 @@ class Sampler:
     def sample(self, logits: torch.Tensor, seqs: List[Sequence]) -> torch.Tensor:
         """logits: [S, V] fp32; returns [S] int64 token ids."""
         logits = self._apply_penalties(logits, seqs)
+        if self.backend == "fused":
+            return self._sample_fused(logits, seqs)
         greedy = logits.argmax(dim=-1)
         # host-side check: avoids a device sync on the (common) all-greedy
         # decode step
@@ -135,3 +157,50 @@ class Sampler:
             ).squeeze(1)
             sampled[rows] = draw
         return sampled
+
+    def _sample_fused(self, logits: torch.Tensor, seqs: List[Sequence]):
+        """One ops.sample_tokens call for the whole mixed batch. The per-row
+        parameters are laid out in one host buffer of 8 int32 words per row
+        (temperature | top_k | top_p | min_p | rng as 2 x int64) and reach
+        the device in a single copy. Seeded rows draw at (seed,
+        len(output_token_ids)), unseeded rows at (engine seed, 2^62 +
+        running counter): a token depends only on its row and that pair."""
+        from fusioninfer_amd import ops
+
+        T = len(seqs)
+        temps, ks, ps, mps, rng = [], [], [], [], []
+        for s in seqs:
+            sp = s.sampling
+            temps.append(sp.temperature)
+            ks.append(min(max(int(sp.top_k), 0), 2**31 - 1))
+            ps.append(sp.top_p)
+            mps.append(sp.min_p)
+            if sp.temperature == 0:
+                rng.append((0, 0))
+            elif sp.seed is not None:
+                rng.append((_as_i64(sp.seed), len(s.output_token_ids)))
+            else:
+                rng.append((
+                    _as_i64(self.base_seed),
+                    _as_i64(_UNSEEDED_OFFSET_BASE + self.num_unseeded_draws),
+                ))
+                self.num_unseeded_draws += 1
+        host = torch.empty(8 * T, dtype=torch.int32)
+        host[:T].view(torch.float32).copy_(torch.tensor(temps))
+        host[T:2 * T].copy_(torch.tensor(ks, dtype=torch.int32))
+        host[2 * T:3 * T].view(torch.float32).copy_(torch.tensor(ps))
+        host[3 * T:4 * T].view(torch.float32).copy_(torch.tensor(mps))
+        host[4 * T:].view(torch.int64).copy_(
+            torch.tensor(rng, dtype=torch.int64).flatten()
+        )
+        dev = host.to(logits.device)
+        if logits.dtype != torch.float32:
+            logits = logits.float()
+        return ops.sample_tokens(
+            logits.contiguous(),
+            dev[:T].view(torch.float32),
+            dev[T:2 * T],
+            dev[2 * T:3 * T].view(torch.float32),
+            dev[3 * T:4 * T].view(torch.float32),
+            dev[4 * T:].view(torch.int64).view(T, 2),
+        )

@@ -486,4 +486,50 @@ def lora_apply(out, x, slot_ids, a_stack, b_stack, scales):
     return ref.lora_apply(out, x, slot_ids, a_stack, b_stack, scales)
 
 
+# ---------------------------------------------------------------- sampling
+
+def sample_tokens(logits, temperature, top_k, top_p, min_p, rng):
+    """Fused sampling, one token per row: greedy when temperature == 0,
+    otherwise temperature scaling, top-k (0 < k < V), top-p (p < 1),
+    min-p (> 0) and a Philox4x32-10 draw keyed by rng[t] = (seed, offset).
+    Fixed-point integer masses make the result a pure function of the row,
+    its parameters and its rng pair (see reference.sample_row).
+
+    logits [T, V] fp32, temperature / top_p / min_p [T] fp32, top_k [T]
+    int32, rng [T, 2] int64. Returns [T] int64. One launch, static grid,
+    no host sync. Shape or dtype mismatch raises ValueError."""
+    if logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1:
+        raise ValueError(
+            f"sample_tokens: logits must be [T >= 1, V >= 1], got "
+            f"{tuple(logits.shape)}"
+        )
+    T = logits.shape[0]
+    for name, t, dtype, shape in (
+        ("logits", logits, torch.float32, tuple(logits.shape)),
+        ("temperature", temperature, torch.float32, (T,)),
+        ("top_k", top_k, torch.int32, (T,)),
+        ("top_p", top_p, torch.float32, (T,)),
+        ("min_p", min_p, torch.float32, (T,)),
+        ("rng", rng, torch.int64, (T, 2)),
+    ):
+        if t.dtype != dtype or tuple(t.shape) != shape:
+            raise ValueError(
+                f"sample_tokens: {name} must be {dtype} {shape}, got "
+                f"{t.dtype} {tuple(t.shape)}"
+            )
+        if t.device != logits.device:
+            raise ValueError(f"sample_tokens: {name} is on {t.device}, "
+                             f"logits on {logits.device}")
+    if logits.is_cuda:
+        _require_native()
+        out = torch.empty(T, dtype=torch.int64, device=logits.device)
+        _C.sample_tokens(
+            out, logits.contiguous(), temperature.contiguous(),
+            top_k.contiguous(), top_p.contiguous(), min_p.contiguous(),
+            rng.contiguous(),
+        )
+        return out
+    return ref.sample_tokens(logits, temperature, top_k, top_p, min_p, rng)
+
+
 compute_cos_sin_cache = ref.compute_cos_sin_cache

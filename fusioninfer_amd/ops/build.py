@@ -28,6 +28,7 @@ SOURCES = [
     "prefill_attention.hip",
     "moe_gemm.hip",
     "lora.hip",
+    "sampling.hip",
 ]
 
 

@@ -48,6 +48,9 @@ void launch_moe_combine(u16*, const u16*, const int*, const float*, int, int,
 void launch_lora_apply(u16*, u16*, const u16*, const int*, const u16*,
                        const u16*, const float*, int, int, int, int, int,
                        hipStream_t);
+void launch_sample_tokens(int64_t*, const float*, const float*, const int*,
+                          const float*, const float*, const int64_t*, int,
+                          int, hipStream_t);
 
 }  // namespace fi
 
@@ -505,6 +508,37 @@ void lora_apply(at::Tensor out, at::Tensor y_ws, at::Tensor x,
                         static_cast<int>(S), current_stream());
 }
 
+void sample_tokens(at::Tensor out, at::Tensor logits, at::Tensor temperature,
+                   at::Tensor top_k, at::Tensor top_p, at::Tensor min_p,
+                   at::Tensor rng) {
+  TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == at::kFloat &&
+              logits.is_contiguous() && logits.dim() == 2,
+              "sample_tokens: logits must be a contiguous [T, V] fp32 GPU "
+              "tensor");
+  const int64_t T = logits.size(0);
+  const int64_t V = logits.size(1);
+  TORCH_CHECK(T >= 1 && T < (1LL << 31) && V >= 1 && V < (1LL << 30),
+              "sample_tokens: need 1 <= T < 2^31 and 1 <= V < 2^30");
+  auto check_row = [&](const at::Tensor& t, at::ScalarType ty, int64_t n,
+                       const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == ty && t.is_contiguous() &&
+                    t.numel() == n,
+                "sample_tokens: bad ", name);
+  };
+  check_row(out, at::kLong, T, "out");
+  check_row(temperature, at::kFloat, T, "temperature");
+  check_row(top_k, at::kInt, T, "top_k");
+  check_row(top_p, at::kFloat, T, "top_p");
+  check_row(min_p, at::kFloat, T, "min_p");
+  check_row(rng, at::kLong, 2 * T, "rng");
+  fi::launch_sample_tokens(
+      out.data_ptr<int64_t>(), logits.data_ptr<float>(),
+      temperature.data_ptr<float>(), top_k.data_ptr<int>(),
+      top_p.data_ptr<float>(), min_p.data_ptr<float>(),
+      rng.data_ptr<int64_t>(), static_cast<int>(T), static_cast<int>(V),
+      current_stream());
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -544,4 +578,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lora_apply", &lora_apply,
         "batched multi-LoRA shrink + expand indexed by per-token slot ids "
         "(in-place on out)");
+  m.def("sample_tokens", &sample_tokens,
+        "fused temperature / top-k / top-p / min-p sampling with a "
+        "counter-based (Philox4x32-10) draw, one workgroup per row");
 }

@@ -395,3 +395,132 @@ def lora_apply(out, x, slot_ids, a_stack, b_stack, scales):
             out[rows].float() + float(scales[s]) * delta
         ).to(out.dtype)
     return out
+
+
+# ---------------------------------------------------------------- sampling
+
+_M32 = 0xFFFFFFFF
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 (Salmon et al., SC'11) in pure Python integers.
+    counter: 4 u32 words, key: 2 u32 words; returns the 4 output words."""
+    c0, c1, c2, c3 = (int(c) & _M32 for c in counter)
+    k0, k1 = (int(k) & _M32 for k in key)
+    for _ in range(10):
+        p0 = 0xD2511F53 * c0
+        p1 = 0xCD9E8D57 * c2
+        c0, c1, c2, c3 = (
+            (p1 >> 32) ^ c1 ^ k0, p1 & _M32, (p0 >> 32) ^ c3 ^ k1, p0 & _M32,
+        )
+        k0 = (k0 + 0x9E3779B9) & _M32
+        k1 = (k1 + 0xBB67AE85) & _M32
+    return (c0, c1, c2, c3)
+
+
+def sample_row(x, temperature, top_k, top_p, min_p, seed, offset,
+               slack: float = 0.0):
+    """One row of sample_tokens. Returns (token, margin, kept): kept is the
+    bool mask of tokens that survive the filters (None for a greedy or
+    non-finite row, whose margin is inf). `slack` widens the top-p test by
+    slack * Z_k and the min-p test by slack * min_p in the keep direction
+    (for set-membership checks of tokens drawn with another expf).
+
+    Semantics (shared with sampling.hip): z = x / max(temperature, 1e-5),
+    m = max z, w = floor(exp(z - m) * 2^32) as integers; top-k keeps
+    z >= k-th largest (ties kept); top-p keeps i iff the mass of top-k
+    survivors strictly above z_i is <= floor(floor(p * 2^32) * Z_k / 2^32);
+    min-p keeps exp(z - m) >= min(min_p, 1); the draw takes
+    r = (philox(seed, offset)[0] * Z) >> 32 and returns the first kept
+    index whose inclusive prefix mass exceeds r. Tokens more than ~22.18
+    below the max have w = 0 and are unreachable."""
+    x = x.detach().to("cpu", torch.float32)
+    V = x.numel()
+    best = x.max()
+    bi = int((x == best).nonzero()[0]) if not torch.isnan(best) else 0
+    inf = float("inf")
+    temp = torch.as_tensor(temperature, dtype=torch.float32)
+    if float(temp) == 0.0 or not (-inf < float(best) < inf):
+        return (bi if float(best) > -inf else 0), inf, None
+    t = temp.clamp(min=1e-5)
+    z = x / t + 0.0
+    m = z.max()
+    e = torch.exp(z - m)
+    w = torch.floor(e.double() * 4294967296.0).to(torch.int64)
+    keep = torch.ones(V, dtype=torch.bool)
+    margin = inf
+    k = int(top_k)
+    if 0 < k < V:
+        keep &= z >= torch.topk(z, k).values[-1]
+    p = float(torch.as_tensor(top_p, dtype=torch.float32))
+    if p < 1.0:
+        p_fix = int(p * 4294967296.0) if p > 0.0 else 0
+        s_idx = keep.nonzero().flatten()
+        zs, order = z[s_idx].sort(descending=True, stable=True)
+        ws = w[s_idx][order]
+        zk = int(ws.sum())
+        P = (p_fix * zk) >> 32
+        _, inverse, counts = torch.unique_consecutive(
+            zs, return_inverse=True, return_counts=True
+        )
+        group_mass = torch.zeros(counts.numel(), dtype=torch.int64)
+        group_mass.index_add_(0, inverse, ws)
+        above = (group_mass.cumsum(0) - group_mass)[inverse]
+        dist = (above - P).abs().min()
+        margin = min(margin, float(dist) / zk)
+        keep_s = above <= P + int(slack * zk)
+        keep = torch.zeros(V, dtype=torch.bool)
+        keep[s_idx[order[keep_s]]] = True
+    mp = min(float(torch.as_tensor(min_p, dtype=torch.float32)), 1.0)
+    if mp > 0.0:
+        # expf errors are relative to the weight itself (<= min_p * 2^32
+        # near the flip point), so this test's margin and slack are taken
+        # relative to the threshold, which is tighter than relative to Z
+        keep_mp = e >= torch.tensor(mp, dtype=torch.float32)
+        mp_w = mp * 4294967296.0
+        dist = (w[keep].double() - mp_w).abs().min()
+        margin = min(margin, float(dist) / mp_w)
+        if slack > 0.0:
+            keep_mp = w.double() >= mp_w * (1.0 - slack)
+        keep &= keep_mp
+    wk = torch.where(keep, w, torch.zeros_like(w))
+    cum = wk.cumsum(0)
+    Z = int(cum[-1])
+    u = philox4x32_10(
+        (int(offset) & _M32, (int(offset) >> 32) & _M32, 0, 0),
+        (int(seed) & _M32, (int(seed) >> 32) & _M32),
+    )[0]
+    r = (u * Z) >> 32
+    tok = int(torch.searchsorted(cum, torch.tensor(r), right=True))
+    incl = int(cum[tok])
+    excl = incl - int(wk[tok])
+    if excl > 0:
+        margin = min(margin, (r - excl) / Z)
+    if incl < Z:
+        margin = min(margin, (incl - r) / Z)
+    return tok, margin, keep
+
+
+def sample_tokens(logits, temperature, top_k, top_p, min_p, rng,
+                  return_margin: bool = False):
+    """Reference of the fused sampling kernel: logits [T, V] fp32,
+    temperature / top_p / min_p [T] fp32, top_k [T] int32, rng [T, 2]
+    int64 (seed, offset). Returns [T] int64 tokens; with return_margin
+    also a [T] float64 tensor with, per row, the smallest relative
+    distance (in units of the mass it is compared against) between any
+    comparison made (top-p mass test, min-p test, r against the two
+    neighbouring prefix sums) and its flip point — inf for greedy rows."""
+    T = logits.shape[0]
+    toks, margins = [], []
+    rng_l = rng.tolist()
+    for i in range(T):
+        tok, mg, _ = sample_row(
+            logits[i], temperature[i], top_k[i], top_p[i], min_p[i],
+            rng_l[i][0], rng_l[i][1],
+        )
+        toks.append(tok)
+        margins.append(mg)
+    out = torch.tensor(toks, dtype=torch.int64, device=logits.device)
+    if return_margin:
+        return out, torch.tensor(margins, dtype=torch.float64)
+    return out

@@ -38,6 +38,10 @@ def parse_args(argv=None):
                         '"kv_role": "kv_producer"|"kv_consumer"}')
     p.add_argument("--enforce-eager", action="store_true")
     p.add_argument("--quantization", choices=["fp8"], default=None)
+    p.add_argument("--sampler-backend", choices=["torch", "fused"],
+                   default="torch",
+                   help="fused: one HIP sampling launch per step "
+                        "(top-k/top-p/min-p, counter-based seeded draws)")
     p.add_argument("--kv-cache-dtype", choices=["auto", "fp8"], default="auto")
     p.add_argument("--swap-space", type=float, default=0.0,
                    help="GiB of CPU swap for preempted sequences (0=recompute)")
@@ -145,6 +149,7 @@ def build_engine_config(args):
         enable_lora=args.enable_lora,
         max_lora_rank=args.max_lora_rank,
         enforce_eager=args.enforce_eager,
+        sampler_backend=args.sampler_backend,
     )
 
 

@@ -1,6 +1,7 @@
 """Microbenchmarks for the FusionInfer-AMD HIP kernels (run on a GPU box).
 
-Usage: python tools/bench_kernels.py [prefill|decode|elementwise|lora|all]
+Usage: python tools/bench_kernels.py
+           [prefill|decode|elementwise|lora|sampling|sampling_e2e|all]
 Prints per-shape timing + achieved TFLOP/s (attention) or GB/s (memory ops).
 """
 
@@ -129,6 +130,140 @@ def bench_lora():
                       f"{tl*1e6:.1f} | {tl/tk:.2f}x |")
 
 
+def _event_times_us(fn, iters):
+    """Per-call device-event times (us), one synchronise at the end."""
+    evs = [(torch.cuda.Event(enable_timing=True),
+            torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
+    for a, b in evs:
+        a.record()
+        fn()
+        b.record()
+    torch.cuda.synchronize()
+    return [a.elapsed_time(b) * 1e3 for a, b in evs]
+
+
+def _median(xs):
+    xs = sorted(xs)
+    return xs[len(xs) // 2]
+
+
+def bench_sampling():
+    """Sampler.sample with the torch and the fused backend on the same
+    logits (V = 151936, Qwen3), per parameter mix. Device-event time per
+    call (host work that delays the queue included), median of 3
+    alternating rounds x 20 calls after a warm-up of each; `kernel` is
+    ops.sample_tokens alone on prebuilt device parameters."""
+    from fusioninfer_amd.engine.sampler import Sampler
+    from fusioninfer_amd.engine.sequence import SamplingParams, Sequence
+
+    V = 151936
+    mixes = {
+        "greedy": lambda i: dict(),
+        "top_p 0.9": lambda i: dict(temperature=0.7, top_p=0.9),
+        "top_k 50 + top_p 0.9 + min_p 0.05": lambda i: dict(
+            temperature=0.7, top_k=50, top_p=0.9, min_p=0.05),
+        "top_p 0.9, half seeded": lambda i: dict(
+            temperature=0.7, top_p=0.9, seed=(i if i % 2 else None)),
+    }
+    print("== Sampler.sample, torch vs fused backend (V=151936, fp32) ==")
+    print("| mix | T | torch us | fused us | kernel us | torch/fused |")
+    print("|---|---|---|---|---|---|")
+    for T in (8, 64, 256):
+        logits = torch.randn(T, V, device="cuda") * 4
+        for name, mk in mixes.items():
+            seqs = []
+            for i in range(T):
+                s = Sequence(f"s{i}", [1, 2, 3], SamplingParams(**mk(i)))
+                s.output_token_ids = [0] * (i % 7)
+                seqs.append(s)
+            samplers = {
+                b: Sampler(0, "cuda", backend=b) for b in ("torch", "fused")
+            }
+            sp = [s.sampling for s in seqs]
+            params = (
+                torch.tensor([p.temperature for p in sp], device="cuda"),
+                torch.tensor([p.top_k for p in sp], dtype=torch.int32,
+                             device="cuda"),
+                torch.tensor([p.top_p for p in sp], device="cuda"),
+                torch.tensor([p.min_p for p in sp], device="cuda"),
+                torch.tensor([[p.seed or 0, i] for i, p in enumerate(sp)],
+                             dtype=torch.int64, device="cuda"),
+            )
+            fns = {
+                "torch": lambda: samplers["torch"].sample(logits, seqs),
+                "fused": lambda: samplers["fused"].sample(logits, seqs),
+                "kernel": lambda: ops.sample_tokens(logits, *params),
+            }
+            times = {k: [] for k in fns}
+            for k, fn in fns.items():
+                for _ in range(5):
+                    fn()
+            torch.cuda.synchronize()
+            for _ in range(3):
+                for k, fn in fns.items():
+                    times[k] += _event_times_us(fn, 20)
+            med = {k: _median(v) for k, v in times.items()}
+            print(f"| {name} | {T} | {med['torch']:.1f} | {med['fused']:.1f} "
+                  f"| {med['kernel']:.1f} | "
+                  f"{med['torch'] / med['fused']:.2f}x |", flush=True)
+
+
+def bench_sampling_e2e():
+    """End-to-end: the 4-layer Qwen3-0.6B test engine, 64 seeded sampled
+    sequences (temperature 0.8, top_p 0.9), 64 tokens each, both sampler
+    backends. One untimed generation first (graph replays, allocator),
+    then one timed: wall ms per engine step and pipelined steps taken."""
+    from fusioninfer_amd.config import (CacheConfig, EngineConfig,
+                                        SchedulerConfig)
+    from fusioninfer_amd.engine.llm_engine import LLMEngine
+    from fusioninfer_amd.engine.sequence import SamplingParams
+    from fusioninfer_amd.models.registry import get_model_config
+
+    print("== engine decode, 64 seeded sampled sequences (4-layer "
+          "Qwen3-0.6B) ==")
+    print("| backend | steps | ms/step | num_async_steps |")
+    print("|---|---|---|---|")
+    for backend in ("torch", "fused"):
+        mc = get_model_config("Qwen3-0.6B")
+        mc.num_layers = 4
+        cfg = EngineConfig(
+            model=mc,
+            cache=CacheConfig(num_gpu_blocks=2048),
+            scheduler=SchedulerConfig(
+                max_num_seqs=64, max_num_batched_tokens=4096,
+                max_model_len=512,
+            ),
+            seed=7,
+            sampler_backend=backend,
+        )
+        torch.manual_seed(0)
+        eng = LLMEngine(cfg, device="cuda:0")
+
+        def run():
+            for i in range(64):
+                eng.add_request(
+                    [(7 * i + j) % 1000 + 10 for j in range(32)],
+                    SamplingParams(max_tokens=64, temperature=0.8,
+                                   top_p=0.9, seed=100 + i),
+                )
+            steps0, async0 = eng.num_steps, eng.num_async_steps
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            while eng.has_unfinished():
+                eng.step()
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            return (dt, eng.num_steps - steps0,
+                    eng.num_async_steps - async0)
+
+        run()
+        dt, steps, n_async = run()
+        print(f"| {backend} | {steps} | {dt / steps * 1e3:.2f} | {n_async} |",
+              flush=True)
+        del eng
+        torch.cuda.empty_cache()
+
+
 class _OneTarget:
     """Minimal stand-in for LoRASlots: one layer, one target."""
 
@@ -148,3 +283,7 @@ if __name__ == "__main__":
         bench_elementwise()
     if which in ("lora", "all"):
         bench_lora()
+    if which in ("sampling", "all"):
+        bench_sampling()
+    if which in ("sampling_e2e", "all"):
+        bench_sampling_e2e()

@@ -372,6 +372,106 @@ def test_paged_attention_decode_fp8kv(group, seq_lens):
     assert_close_bf16(out.cpu(), expected, atol=tol, rtol=tol)
 
 
+# The launcher picks 8-wave "wide" kernels while seqs * kv_heads *
+# partitions < 256 and 4-wave "full-grid" kernels from there on; every
+# case above is wide. 64 sequences x 2 kv heads x 2 partitions (a
+# 64-block table) is the smallest full grid. Its lengths leave the second
+# partition empty (<= 512), leave waves without a chunk (1, 5, 16) and end
+# in a partial block (5, 17, 255, 513, 1000).
+DECODE_RAGGED = [1, 5, 16, 17, 255, 1023]
+DECODE_FULL_GRID = [1, 5, 16, 17, 255, 512, 513, 1000] * 8
+DECODE_FULL_GRID_BLOCKS = 64
+
+
+def _decode_inputs(group, seq_lens, head_dim, fp8, table_blocks=None):
+    """Seeded q / paged cache / block table / lengths for one decode case,
+    blocks assigned sequentially from 1 (block 0 backs the unused table
+    entries)."""
+    torch.manual_seed(7000 + 100 * group + head_dim + int(fp8) + len(seq_lens))
+    Hk, bs = 2, 16
+    S = len(seq_lens)
+    nblk = [(L + bs - 1) // bs for L in seq_lens]
+    max_blocks = table_blocks or max(nblk)
+    total_blocks = sum(nblk) + 2
+    q = torch.randn(S, Hk * group, head_dim, dtype=torch.bfloat16, device=DEV)
+    k_cache = torch.randn(total_blocks, Hk, bs, head_dim,
+                          dtype=torch.bfloat16, device=DEV)
+    v_cache = torch.randn_like(k_cache)
+    if fp8:
+        k_cache, v_cache = _fp8_cache(k_cache), _fp8_cache(v_cache)
+    bt = torch.zeros(S, max_blocks, dtype=torch.int32, device=DEV)
+    nxt = 1
+    for s, n in enumerate(nblk):
+        bt[s, :n] = torch.arange(nxt, nxt + n, dtype=torch.int32)
+        nxt += n
+    lens = torch.tensor(seq_lens, dtype=torch.int32, device=DEV)
+    return q, k_cache, v_cache, bt, lens
+
+
+def _check_paged_decode(group, seq_lens, head_dim=128, fp8=False,
+                        table_blocks=None, tol=3e-2):
+    q, k_cache, v_cache, bt, lens = _decode_inputs(
+        group, seq_lens, head_dim, fp8, table_blocks)
+    scale = 1.0 / math.sqrt(head_dim)
+    out = ops.paged_attention_decode(q, k_cache, v_cache, bt, lens, scale)
+    expected = ref.paged_attention_decode(
+        q.cpu(), k_cache.cpu(), v_cache.cpu(), bt.cpu(), lens.cpu(), scale
+    )
+    assert_close_bf16(out.cpu(), expected, atol=tol, rtol=tol)
+
+
+def _decode_tol(group, fp8):
+    # fp8 G=8 dispatches the fp8 MFMA scores, which quantize Q to e4m3
+    # per head (see test_paged_attention_decode_fp8kv)
+    return 6e-2 if fp8 and group == 8 else 3e-2
+
+
+@pytest.mark.parametrize("fp8", [False, True])
+@pytest.mark.parametrize("group", [1, 2, 4, 8])
+def test_paged_attention_decode_full_grid(group, fp8):
+    """The 4-wave kernels serving batches run, including the head-split
+    G=4 (two waves per chunk stream) and G=8 variants."""
+    _check_paged_decode(group, DECODE_FULL_GRID, fp8=fp8,
+                        table_blocks=DECODE_FULL_GRID_BLOCKS,
+                        tol=_decode_tol(group, fp8))
+
+
+@pytest.mark.parametrize("fp8", [False, True])
+@pytest.mark.parametrize("group", [1, 2, 4, 8])
+@pytest.mark.parametrize("head_dim", [64, 128])
+def test_paged_attention_decode_head_dims_and_groups(head_dim, group, fp8):
+    _check_paged_decode(group, DECODE_RAGGED, head_dim=head_dim, fp8=fp8,
+                        tol=_decode_tol(group, fp8))
+
+
+_SCALAR_SCORES_CHILD = """
+import sys
+sys.path.insert(0, sys.argv[1])
+import test_ops_gpu as t
+t.setup_module()
+for group, fp8 in ((1, False), (4, False), (8, False), (8, True)):
+    t._check_paged_decode(group, t.DECODE_RAGGED, fp8=fp8)
+for group, fp8 in ((4, False), (8, True)):
+    t._check_paged_decode(group, t.DECODE_FULL_GRID, fp8=fp8,
+                          table_blocks=t.DECODE_FULL_GRID_BLOCKS)
+"""
+
+
+def test_paged_attention_decode_scalar_scores():
+    """FI_DECODE_MFMA=0 selects the scalar-FMA scores for every shape. The
+    knob is read once per process, so the cases run in one child; any
+    mismatch there raises and the child exits non-zero. The scalar path
+    keeps Q in fp32, so fp8 G=8 holds the tight 3e-2 here."""
+    tests_dir = os.path.dirname(os.path.abspath(__file__))
+    child = subprocess.run(
+        [sys.executable, "-c", _SCALAR_SCORES_CHILD, tests_dir],
+        env={**os.environ, "FI_DECODE_MFMA": "0"},
+        cwd=os.path.dirname(tests_dir), capture_output=True, text=True,
+        timeout=300,
+    )
+    assert child.returncode == 0, child.stderr[-2000:]
+
+
 @pytest.mark.parametrize("head_dim", [64, 128])
 @pytest.mark.parametrize(
     "ctx_lens,new_lens",

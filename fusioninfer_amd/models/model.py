@@ -12,6 +12,7 @@ vLLM images (`vllm serve --model Qwen/Qwen3-8B`, reference README.md:136-148).
 from __future__ import annotations
 
 import math
+import os
 
 import torch
 import torch.nn as nn
@@ -25,6 +26,13 @@ from fusioninfer_amd.distributed.layers import (
     RowParallelLinear,
 )
 from fusioninfer_amd.engine.metadata import AttnMetadata
+
+# FI_FUSED_ROPE_CACHE=0 restores the attention block as it was before the
+# fused kernel: rope_qk_norm_ + reshape_and_cache, and attention outputs
+# allocated by the ops and copied into `out`. Both paths give the same
+# bits; the switch exists for before/after measurements from one build.
+# Read once at import, not per call: the forward is graph-captured.
+_FUSED_ROPE_CACHE = os.environ.get("FI_FUSED_ROPE_CACHE", "1") != "0"
 
 
 class Attention(nn.Module):
@@ -83,17 +91,28 @@ class Attention(nn.Module):
         q = qkv[:, : self.q_size]
         k = qkv[:, self.q_size : self.q_size + self.kv_size]
         v = qkv[:, self.q_size + self.kv_size :]
-        ops.rope_qk_norm_(
-            q, k, meta.positions, cos_sin,
-            self.num_heads, self.num_kv_heads, self.head_dim,
-            self.q_norm_weight, self.k_norm_weight, self.eps,
-        )
         k_cache, v_cache = kv_cache
         fp8_kv = k_cache.dtype == torch.float8_e4m3fn
         ks = self.k_scale if fp8_kv else 1.0
         vs = self.v_scale if fp8_kv else 1.0
-        ops.reshape_and_cache(k, v, k_cache, v_cache, meta.slot_mapping,
-                              1.0 / ks, 1.0 / vs)
+        if _FUSED_ROPE_CACHE:
+            # one pass: q in place, K and V straight to the paged cache
+            # (nothing below reads k or v from qkv again)
+            ops.rope_qk_norm_cache_(
+                q, k, v, meta.positions, cos_sin,
+                self.num_heads, self.num_kv_heads, self.head_dim,
+                k_cache, v_cache, meta.slot_mapping,
+                self.q_norm_weight, self.k_norm_weight, self.eps,
+                1.0 / ks, 1.0 / vs,
+            )
+        else:
+            ops.rope_qk_norm_(
+                q, k, meta.positions, cos_sin,
+                self.num_heads, self.num_kv_heads, self.head_dim,
+                self.q_norm_weight, self.k_norm_weight, self.eps,
+            )
+            ops.reshape_and_cache(k, v, k_cache, v_cache, meta.slot_mapping,
+                                  1.0 / ks, 1.0 / vs)
         # K's dequant scale folds EXACTLY into the softmax scalar:
         # scale*(Q . ks*K8) == (scale*ks)*(Q . K8); V's is a linear
         # post-multiply on the attention output (applied below).
@@ -102,6 +121,11 @@ class Attention(nn.Module):
         T = qkv.shape[0]
         np_, nd = meta.num_prefill_tokens, meta.num_decode_tokens
         out = torch.empty(T, self.q_size, dtype=qkv.dtype, device=qkv.device)
+        # both attention ops write their rows of `out` directly
+        out_p = out_d = None
+        if _FUSED_ROPE_CACHE:
+            out_p = out[:np_].view(np_, self.num_heads, self.head_dim)
+            out_d = out[np_:].view(nd, self.num_heads, self.head_dim)
         if np_ > 0:
             # context attention over the paged cache (the new tokens' K/V
             # were just written above); cached prefixes are never recomputed
@@ -116,8 +140,10 @@ class Attention(nn.Module):
                 tile_seq=meta.tile_seq,
                 tile_row0=meta.tile_row0,
                 tile_rows=meta.tile_rows or None,
+                out=out_p,
             )
-            out[:np_] = o.view(np_, self.q_size)
+            if out_p is None:
+                out[:np_] = o.view(np_, self.q_size)
         if nd > 0:
             o = ops.paged_attention_decode(
                 q[np_:].view(nd, self.num_heads, self.head_dim),
@@ -126,8 +152,10 @@ class Attention(nn.Module):
                 meta.block_tables,
                 meta.seq_lens,
                 scale,
+                out=out_d,
             )
-            out[np_:] = o.view(nd, self.q_size)
+            if out_d is None:
+                out[np_:] = o.view(nd, self.q_size)
         if vs != 1.0:
             out *= vs
         if meta.lora is not None:

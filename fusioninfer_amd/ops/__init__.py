@@ -174,6 +174,62 @@ def reshape_and_cache(k, v, k_cache, v_cache, slot_mapping,
     )
 
 
+def rope_qk_norm_cache_(
+    q: torch.Tensor,          # [T, Hq*D] (row-strided slice OK)
+    k: torch.Tensor,          # [T, Hk*D]
+    v: torch.Tensor,          # [T, Hk*D]
+    positions: torch.Tensor,  # [T] int32
+    cos_sin: torch.Tensor,    # [P, D] fp32
+    num_q_heads: int,
+    num_kv_heads: int,
+    head_dim: int,
+    k_cache: torch.Tensor,    # [B, Hk, 16, D] bf16 or float8_e4m3fn
+    v_cache: torch.Tensor,
+    slot_mapping: torch.Tensor,  # [T] int32, < 0 = padding row
+    q_weight: Optional[torch.Tensor] = None,
+    k_weight: Optional[torch.Tensor] = None,
+    eps: float = 1e-6,
+    k_inv_scale: float = 1.0,
+    v_inv_scale: float = 1.0,
+):
+    """rope_qk_norm_ + reshape_and_cache in one kernel, bit for bit.
+
+    q gets the optional per-head RMSNorm + NeoX RoPE in place. K gets the
+    same and is written to k_cache at slot_mapping[t]; it is NOT written
+    back, so the contents of `k` after the call are unspecified. V is
+    copied to v_cache. Rows with a negative slot skip both cache writes
+    (their q is still processed). fp8 caches take the rows times the
+    inverse scales, as reshape_and_cache does. Returns q.
+
+    The kernel covers head_dim 64 and 128 and the [B, Hk, 16, D] cache
+    layout; anything else raises ValueError on the GPU. On the CPU this is
+    the reference composition (ref.rope_qk_norm, ref.reshape_and_cache)."""
+    if q.is_cuda:
+        _require_native()
+        if head_dim not in (64, 128):
+            raise ValueError(
+                f"rope_qk_norm_cache_: head_dim must be 64 or 128, got "
+                f"{head_dim}")
+        if (k_cache.dim() != 4 or k_cache.shape != v_cache.shape
+                or k_cache.shape[1] != num_kv_heads or k_cache.shape[2] != 16
+                or k_cache.shape[3] != head_dim):
+            raise ValueError(
+                "rope_qk_norm_cache_: caches must both be "
+                f"[B, {num_kv_heads}, 16, {head_dim}], got "
+                f"{tuple(k_cache.shape)} and {tuple(v_cache.shape)}")
+        _C.rope_qk_norm_cache(
+            q, k, v, q_weight, k_weight, cos_sin, positions, k_cache,
+            v_cache, slot_mapping, num_q_heads, num_kv_heads, head_dim, eps,
+            k_inv_scale, v_inv_scale,
+        )
+        return q
+    rope_qk_norm_(q, k, positions, cos_sin, num_q_heads, num_kv_heads,
+                  head_dim, q_weight, k_weight, eps)
+    reshape_and_cache(k, v, k_cache, v_cache, slot_mapping,
+                      k_inv_scale, v_inv_scale)
+    return q
+
+
 def gather_kv_blocks(k_cache, v_cache, block_ids) -> torch.Tensor:
     if k_cache.is_cuda:
         _require_native()
@@ -199,6 +255,18 @@ def scatter_kv_blocks(staging, k_cache, v_cache, block_ids):
 DECODE_PARTITION_TOKENS = 512  # flash-decoding partition size (kernel contract)
 
 
+def _check_attn_out(out: torch.Tensor, q: torch.Tensor) -> None:
+    """`out=` of the attention ops: the kernels index it as a dense
+    [n, Hq, D] bf16 array (a row slice of a larger buffer viewed that way
+    is fine, a column slice is not)."""
+    if (out.shape != q.shape or out.dtype != q.dtype
+            or out.device != q.device or not out.is_contiguous()):
+        raise ValueError(
+            f"out must be a contiguous {tuple(q.shape)} {q.dtype} tensor on "
+            f"{q.device}, got {tuple(out.shape)} {out.dtype} strides "
+            f"{out.stride()} on {out.device}")
+
+
 def paged_attention_decode(
     q: torch.Tensor,            # [S, Hq, D]
     k_cache: torch.Tensor,      # [B, Hk, bs, D]
@@ -206,13 +274,17 @@ def paged_attention_decode(
     block_tables: torch.Tensor,  # [S, max_blocks] int32
     seq_lens: torch.Tensor,      # [S] int32
     scale: Optional[float] = None,
+    out: Optional[torch.Tensor] = None,  # [S, Hq, D] contiguous, written
 ) -> torch.Tensor:
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
+    if out is not None:
+        _check_attn_out(out, q)
     if q.is_cuda:
         _require_native()
         S, Hq, D = q.shape
-        out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+        if out is None:
+            out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
         # partitions from the block-table width: static shape under
         # hipGraph capture (seq_lens vary between replays, width doesn't)
         max_tokens = int(block_tables.shape[1]) * int(k_cache.shape[2])
@@ -233,7 +305,8 @@ def paged_attention_decode(
             ml_ws, acc_ws, num_parts, scale,
         )
         return out
-    return ref.paged_attention_decode(q, k_cache, v_cache, block_tables, seq_lens, scale)
+    res = ref.paged_attention_decode(q, k_cache, v_cache, block_tables, seq_lens, scale)
+    return res if out is None else out.copy_(res)
 
 
 # q rows per prefill workgroup (NW waves x 32) — kernel contract; the
@@ -312,11 +385,14 @@ def prefill_attention_paged(
     tile_seq: Optional[torch.Tensor] = None,
     tile_row0: Optional[torch.Tensor] = None,
     tile_rows: Optional[int] = None,
+    out: Optional[torch.Tensor] = None,  # [Tnew, Hq, D] contiguous, written
 ) -> torch.Tensor:
     """Context attention: new tokens attend over the paged cache (their own
     K/V must already be written via reshape_and_cache)."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
+    if out is not None:
+        _check_attn_out(out, q)
     if q.is_cuda:
         _require_native()
         if tile_seq is None:
@@ -325,16 +401,18 @@ def prefill_attention_paged(
             tile_seq, tile_row0 = build_prefill_tiles(
                 lens, device=q.device, rows=tile_rows
             )
-        out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+        if out is None:
+            out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
         _C.prefill_attention_paged(
             out, q, k_cache, v_cache, tile_seq, tile_row0, cu_seqlens_q,
             block_tables, seq_lens_k, scale,
             tile_rows or PREFILL_TILE_ROWS,
         )
         return out
-    return ref.prefill_attention_paged(
+    res = ref.prefill_attention_paged(
         q, k_cache, v_cache, block_tables, cu_seqlens_q, seq_lens_k, scale
     )
+    return res if out is None else out.copy_(res)
 
 
 # ---------------------------------------------------------------- MoE

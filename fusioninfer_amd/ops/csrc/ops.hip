@@ -22,6 +22,11 @@ void launch_rope_qk_norm(u16*, u16*, int64_t, int64_t, const u16*, const u16*,
 void launch_reshape_and_cache(const u16*, const u16*, void*, void*,
                               const int*, int64_t, int64_t, int, int, int,
                               int, bool, float, float, hipStream_t);
+void launch_rope_qk_norm_cache(u16*, const u16*, const u16*, int64_t, int64_t,
+                               int64_t, const u16*, const u16*, const float*,
+                               const int*, void*, void*, const int*, int, int,
+                               int, int, float, bool, float, float,
+                               hipStream_t);
 template <bool GATHER>
 void launch_kv_block_copy(u16*, u16*, u16*, const int*, int, int64_t,
                           hipStream_t);
@@ -217,6 +222,74 @@ void reshape_and_cache(at::Tensor k, at::Tensor v, at::Tensor k_cache,
       current_stream());
 }
 
+void rope_qk_norm_cache(at::Tensor q, at::Tensor k, at::Tensor v,
+                        c10::optional<at::Tensor> q_weight,
+                        c10::optional<at::Tensor> k_weight, at::Tensor cos_sin,
+                        at::Tensor positions, at::Tensor k_cache,
+                        at::Tensor v_cache, at::Tensor slot_mapping,
+                        int64_t num_q_heads, int64_t num_kv_heads,
+                        int64_t head_dim, double eps, double k_inv_scale,
+                        double v_inv_scale) {
+  CHECK_BF16_CUDA(q);
+  CHECK_BF16_CUDA(k);
+  CHECK_BF16_CUDA(v);
+  TORCH_CHECK(head_dim == 64 || head_dim == 128,
+              "rope_qk_norm_cache: head_dim must be 64 or 128");
+  TORCH_CHECK(num_q_heads >= 1 && num_kv_heads >= 1);
+  const bool fp8 = cache_is_fp8(k_cache);
+  TORCH_CHECK(v_cache.scalar_type() == k_cache.scalar_type() &&
+              k_cache.is_cuda() && v_cache.is_cuda() &&
+              k_cache.is_contiguous() && v_cache.is_contiguous() &&
+              k_cache.dim() == 4 && v_cache.sizes() == k_cache.sizes());
+  TORCH_CHECK(k_cache.size(2) == 16, "cache block_size must be 16");
+  TORCH_CHECK(k_cache.size(1) == num_kv_heads && k_cache.size(3) == head_dim,
+              "rope_qk_norm_cache: cache must be [B, Hk, 16, D]");
+  // q/k/v are row-strided slices of the fused qkv projection output
+  const int64_t tokens = q.size(0);
+  TORCH_CHECK(q.dim() == 2 && k.dim() == 2 && v.dim() == 2);
+  TORCH_CHECK(q.stride(1) == 1 && k.stride(1) == 1 && v.stride(1) == 1);
+  TORCH_CHECK(q.size(1) == num_q_heads * head_dim &&
+              k.size(1) == num_kv_heads * head_dim &&
+              v.size(1) == num_kv_heads * head_dim &&
+              k.size(0) == tokens && v.size(0) == tokens);
+  TORCH_CHECK(tokens < (1LL << 31));
+  TORCH_CHECK(cos_sin.scalar_type() == at::kFloat && cos_sin.is_cuda() &&
+              cos_sin.is_contiguous() && cos_sin.dim() == 2 &&
+              cos_sin.size(1) == head_dim);
+  TORCH_CHECK(positions.scalar_type() == at::kInt && positions.is_cuda() &&
+              positions.is_contiguous() && positions.numel() == tokens);
+  TORCH_CHECK(slot_mapping.scalar_type() == at::kInt &&
+              slot_mapping.is_cuda() && slot_mapping.is_contiguous() &&
+              slot_mapping.numel() == tokens);
+  // every access is 16 B per lane
+  auto aligned16 = [](const at::Tensor& t) {
+    return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+  };
+  TORCH_CHECK(aligned16(q) && aligned16(k) && aligned16(v) &&
+                  aligned16(cos_sin) && aligned16(k_cache) &&
+                  aligned16(v_cache) && q.stride(0) % 8 == 0 &&
+                  k.stride(0) % 8 == 0 && v.stride(0) % 8 == 0,
+              "rope_qk_norm_cache: q/k/v rows and caches must be 16-byte "
+              "aligned");
+  auto weight_ptr = [&](const c10::optional<at::Tensor>& w) -> const u16* {
+    if (!w) return nullptr;
+    CHECK_BF16_CUDA(*w);
+    TORCH_CHECK(w->is_contiguous() && w->numel() == head_dim && aligned16(*w));
+    return bf16_cptr(*w);
+  };
+  const u16* qw = weight_ptr(q_weight);
+  const u16* kw = weight_ptr(k_weight);
+  fi::launch_rope_qk_norm_cache(
+      bf16_ptr(q), bf16_cptr(k), bf16_cptr(v), q.stride(0), k.stride(0),
+      v.stride(0), qw, kw, cos_sin.data_ptr<float>(),
+      positions.data_ptr<int>(), k_cache.data_ptr(), v_cache.data_ptr(),
+      slot_mapping.data_ptr<int>(), static_cast<int>(tokens),
+      static_cast<int>(num_q_heads), static_cast<int>(num_kv_heads),
+      static_cast<int>(head_dim), static_cast<float>(eps), fp8,
+      static_cast<float>(k_inv_scale), static_cast<float>(v_inv_scale),
+      current_stream());
+}
+
 void gather_kv_blocks(at::Tensor staging, at::Tensor k_cache,
                       at::Tensor v_cache, at::Tensor block_ids) {
   TORCH_CHECK(staging.is_cuda() &&
@@ -267,6 +340,8 @@ void paged_attention_decode(at::Tensor out, at::Tensor q, at::Tensor k_cache,
   const int num_kv_heads = k_cache.size(1);
   TORCH_CHECK(k_cache.size(2) == 16, "cache block_size must be 16");
   TORCH_CHECK(q.stride(2) == 1 && q.stride(1) == head_dim);
+  TORCH_CHECK(out.is_contiguous() && out.sizes() == q.sizes(),
+              "out must be a contiguous [S, Hq, D] tensor");
   float* ml = nullptr;
   float* acc = nullptr;
   if (num_parts > 1) {
@@ -332,6 +407,8 @@ void prefill_attention_paged(at::Tensor out, at::Tensor q, at::Tensor k_cache,
   const int num_kv_heads = k_cache.size(1);
   TORCH_CHECK(k_cache.size(2) == 16, "cache block_size must be 16");
   TORCH_CHECK(q.stride(2) == 1 && q.stride(1) == head_dim);
+  TORCH_CHECK(out.is_contiguous() && out.sizes() == q.sizes(),
+              "out must be a contiguous [T, Hq, D] tensor");
   fi::launch_prefill_attn(
       bf16_ptr(out), bf16_cptr(q), k_cache.data_ptr(), v_cache.data_ptr(),
       tile_seq.data_ptr<int>(), tile_row0.data_ptr<int>(),
@@ -555,6 +632,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rope_qk_norm", &rope_qk_norm,
         "fused per-head qk RMSNorm + NeoX RoPE (in-place)");
   m.def("reshape_and_cache", &reshape_and_cache, "scatter K/V into paged cache");
+  m.def("rope_qk_norm_cache", &rope_qk_norm_cache,
+        "fused qk RMSNorm + NeoX RoPE (q in place) + K/V paged-cache write");
   m.def("gather_kv_blocks", &gather_kv_blocks, "pack KV blocks for PD send");
   m.def("scatter_kv_blocks", &scatter_kv_blocks, "unpack KV blocks from PD recv");
   m.def("paged_attention_decode", &paged_attention_decode,

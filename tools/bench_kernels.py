@@ -84,6 +84,56 @@ def bench_elementwise():
         t = timeit(lambda: ops.silu_and_mul(y))
         gb = T * 24576 * 2 * 1.5 / 1e9
         print(f"  silu_and_mul T={T}:       {t*1e6:7.1f} us {gb/t:6.0f} GB/s")
+        _bench_rope_cache(T)
+
+
+def _bench_rope_cache(T):
+    """qk-norm + RoPE + KV-cache write at the Qwen3-8B shape (Hq 32, Hk 8,
+    D 128, qkv row stride 6144, bf16 cache): the two-kernel path
+    (rope_qk_norm_ + reshape_and_cache) and the fused rope_qk_norm_cache_
+    on the same buffers, alternating, best of three rounds. GB/s is over
+    the bytes the result needs, for both: q and k read, q written, v read,
+    both cache rows written (the pair moves more: it writes k back and
+    reads it again)."""
+    Hq, Hk, D, bs = 32, 8, 128, 16
+    qkv = torch.randn(T, (Hq + 2 * Hk) * D, dtype=torch.bfloat16,
+                      device="cuda")
+    q = qkv[:, : Hq * D]
+    k = qkv[:, Hq * D : (Hq + Hk) * D]
+    v = qkv[:, (Hq + Hk) * D :]
+    qw = torch.randn(D, dtype=torch.bfloat16, device="cuda")
+    kw = torch.randn(D, dtype=torch.bfloat16, device="cuda")
+    pos = torch.arange(T, dtype=torch.int32, device="cuda") % 1152
+    cos_sin = ops.compute_cos_sin_cache(D, 1152, 1e6).to("cuda")
+    nblocks = (T + bs - 1) // bs
+    k_cache = torch.zeros(nblocks, Hk, bs, D, dtype=torch.bfloat16,
+                          device="cuda")
+    v_cache = torch.zeros_like(k_cache)
+    slots = torch.randperm(nblocks * bs, device="cuda")[:T].int()
+
+    def pair():
+        ops.rope_qk_norm_(q, k, pos, cos_sin, Hq, Hk, D, qw, kw, 1e-6)
+        ops.reshape_and_cache(k, v, k_cache, v_cache, slots)
+
+    def fused():
+        ops.rope_qk_norm_cache_(q, k, v, pos, cos_sin, Hq, Hk, D, k_cache,
+                                v_cache, slots, qw, kw, 1e-6)
+
+    def rope_only():
+        ops.rope_qk_norm_(q, k, pos, cos_sin, Hq, Hk, D, qw, kw, 1e-6)
+
+    tp = tf = tr = float("inf")
+    for _ in range(3):
+        tp = min(tp, timeit(pair, iters=50))
+        tf = min(tf, timeit(fused, iters=50))
+        tr = min(tr, timeit(rope_only, iters=50))
+        # q is renormalised in place every call; keep it O(1)
+        qkv.normal_()
+    gb = T * D * 2 * (2 * Hq + 4 * Hk) / 1e9
+    print(f"  rope+cache pair T={T}:    {tp*1e6:7.1f} us {gb/tp:6.0f} GB/s"
+          f"  (rope_qk_norm_ alone {tr*1e6:.1f} us)")
+    print(f"  rope_qk_norm_cache_ T={T}:{tf*1e6:7.1f} us {gb/tf:6.0f} GB/s"
+          f"  ({tp/tf:.2f}x)")
 
 
 def bench_lora():

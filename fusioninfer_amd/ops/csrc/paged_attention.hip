@@ -26,6 +26,16 @@
 // seq_lens[s] == 0 with a one-partition table takes the empty-partition
 // branch, which writes to the workspace — null when there is one partition.
 //
+// Known gap (pad slots must hold finite V): phase B multiplies all 16 V
+// rows of a sequence's last block by p and relies on p == 0 for the pad
+// rows, so a NaN or Inf in a V pad slot reaches the output as 0 * NaN.
+// The engine zero-initialises the cache and the fp8 writers saturate; such
+// a value can only be a non-finite bf16 activation left by a previous
+// owner of the block. Finite pad contents of any size are harmless
+// (tests/test_attention_adversarial_gpu.py fills them with poison). A
+// select on vball in the hot loop would close the gap; its cost has not
+// been measured.
+//
 // Capability parity: the paged-attention decode the reference delegates to
 // its vLLM containers (SURVEY.md §2.3 "Paged-attention decode kernel").
 

@@ -151,4 +151,12 @@ class EngineConfig:
     # per step (counter-based seeded draws, keeps seeded requests on the
     # pipelined-decode chain).
     sampler_backend: str = "torch"
+    # Fused backend only: repetition / presence / frequency penalties run
+    # from per-sequence token histograms kept on the device ([penalty_slots,
+    # vocab] int32, allocated on the first penalised request), so such
+    # sequences stay on the pipelined-decode chain. A penalised sequence
+    # beyond penalty_slots takes the host path. device_penalties=False is
+    # the A/B switch back to the host path for all of them.
+    penalty_slots: int = 64
+    device_penalties: bool = True
     enforce_eager: bool = False            # True disables hipGraph decode capture

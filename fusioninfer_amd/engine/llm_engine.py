@@ -86,7 +86,9 @@ class LLMEngine:
                 and cfg.parallel.pipeline_parallel_size == 1):
             self.scheduler.swap_out_fn = self._swap_out
         self.sampler = Sampler(cfg.seed, device,
-                               backend=cfg.sampler_backend)
+                               backend=cfg.sampler_backend,
+                               penalty_slots=cfg.penalty_slots,
+                               device_penalties=cfg.device_penalties)
         from fusioninfer_amd.engine.spec_decode import build_proposer
 
         if (cfg.speculative is not None
@@ -284,6 +286,7 @@ class LLMEngine:
             return False
         if self.proposer is not None:
             self.proposer.release(seq)
+        self.sampler.release_penalty_slot(seq)
         staging = self._swapped.pop(request_id, None)
         if staging is not None:
             self._swap_bytes -= staging.numel() * staging.element_size()
@@ -486,6 +489,9 @@ class LLMEngine:
         if batch.is_empty:
             return pre
         self.num_preemptions += len(batch.preempted)
+        for seq in batch.preempted:
+            # the histogram row is rebuilt when the sequence samples again
+            self.sampler.release_penalty_slot(seq)
         want_plp = any(
             s.sampling.prompt_logprobs is not None for s in batch.prefill_seqs
         )
@@ -554,6 +560,8 @@ class LLMEngine:
             and tp == 1
             and payload.get("logits_rows") is None
             and all(self._seq_async_ok(s) for s in batch.decode_seqs)
+            # enough free penalty slots for all newcomers of the batch
+            and self.sampler.penalty_slots_cover(batch.decode_seqs)
         ):
             # enter the pipelined-decode chain: sample WITHOUT a host
             # sync and defer emission to the next step() call (which
@@ -616,6 +624,7 @@ class LLMEngine:
     def _finish_seq(self, seq: Sequence) -> None:
         if self.proposer is not None:
             self.proposer.release(seq)
+        self.sampler.release_penalty_slot(seq)
         seq.finish_time = time.monotonic()
         self.scheduler.finish(seq)
         self.num_finished += 1
@@ -663,17 +672,24 @@ class LLMEngine:
     def _seq_async_ok(self, s: Sequence) -> bool:
         """Pipeline-eligible: nothing about next-step sampling may depend
         on THIS step's token value on the host (guided masks, penalties
-        over emitted tokens) and nothing extra is read back (logprobs)."""
+        over emitted tokens unless their histogram lives on the device)
+        and nothing extra is read back (logprobs)."""
         sp = s.sampling
         return (
             sp.guided is None
             and not sp.logit_bias
             and sp.logprobs is None
             and sp.prompt_logprobs is None
-            and sp.repetition_penalty == 1.0
-            and sp.presence_penalty == 0.0
-            and sp.frequency_penalty == 0.0
             and s.lora_name is None
+            and (
+                (sp.repetition_penalty == 1.0
+                 and sp.presence_penalty == 0.0
+                 and sp.frequency_penalty == 0.0)
+                # fused backend: the sequence holds a slot of the
+                # sampler's device penalty table, or one is free (the
+                # sampler takes it at sample time)
+                or self.sampler.penalty_slot_available(s)
+            )
             # torch backend: seeded draws key on len(output) — one short
             # pre-drain. The fused backend's (seed, len(output)) offset is
             # a host-known integer and _drain_pending runs before the next

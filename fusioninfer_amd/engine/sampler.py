@@ -24,9 +24,133 @@ def _as_i64(v: int) -> int:
     return v - (1 << 64) if v >= (1 << 63) else v
 
 
+def _has_penalties(sp) -> bool:
+    return (
+        sp.repetition_penalty != 1.0
+        or sp.presence_penalty != 0.0
+        or sp.frequency_penalty != 0.0
+    )
+
+
+def penalty_params(sp):
+    """One row of ops.apply_penalties' params: (rp, inv_rp, presence,
+    frequency), to be stored as fp32. inv_rp is the reciprocal taken in
+    double and then rounded to fp32 (1.7 gives 0x3f169697, the fp32
+    quotient 1 / fp32(1.7) would be 0x3f169696). That rule is empirical:
+    it is what reproduces the GPU `x / rp` of the torch build this was
+    developed against, bit for bit, at rp = 1.3, 1.7, 0.8 and 1.05; it is
+    not a documented torch contract. If a torch upgrade makes
+    tests/test_device_penalties_gpu.py fail on repetition-penalised
+    entries only, this is the line to revisit."""
+    rp = float(sp.repetition_penalty)
+    return (rp, 1.0 / rp if rp != 0.0 else float("inf"),
+            sp.presence_penalty, sp.frequency_penalty)
+
+
+class PenaltyTable:
+    """Device-resident token histograms for penalised sequences (the slot
+    idea of lora.LoRASlots): counts [num_slots, V] int32, row = slot. The
+    host keeps seq_id -> slot and, per slot, `counted_len`: the number of
+    tokens of the owner's history the row holds. ops.apply_penalties reads
+    the rows, one ops.penalty_counts_add per step adds the sampled ids
+    device to device, so a penalised sequence needs no host round trip
+    between steps.
+
+    The table is allocated on the first sync() that has a slot to fill. A
+    row is (re)built from seq.all_token_ids whenever counted_len differs
+    from the history length: first use, preemption-recompute, a discarded
+    late token, tokens appended by another path. Reuse of a released slot
+    is safe by stream order: the next owner's zero and build are enqueued
+    after any add still in flight."""
+
+    def __init__(self, num_slots: int, device: str = "cpu"):
+        self.num_slots = max(int(num_slots), 0)
+        self.device = device
+        self.counts = None  # [num_slots, V] int32, allocated lazily
+        self._slot_of = {}  # seq_id -> slot
+        self._counted_len = {}  # slot -> tokens held, -1 = never built
+        self._free = list(range(self.num_slots - 1, -1, -1))
+        self.num_rebuilds = 0
+
+    def slot_of(self, seq: Sequence) -> int:
+        return self._slot_of.get(seq.seq_id, -1)
+
+    def acquire(self, seq: Sequence) -> int:
+        """The sequence's slot, taking a free one if it has none; -1 when
+        the table is full."""
+        slot = self._slot_of.get(seq.seq_id)
+        if slot is not None:
+            return slot
+        if not self._free:
+            return -1
+        slot = self._free.pop()
+        self._slot_of[seq.seq_id] = slot
+        self._counted_len[slot] = -1
+        return slot
+
+    def release(self, seq: Sequence) -> None:
+        slot = self._slot_of.pop(seq.seq_id, None)
+        if slot is not None:
+            del self._counted_len[slot]
+            self._free.append(slot)
+
+    def sync(self, seqs: List[Sequence], vocab_size: int) -> List[int]:
+        """Slot per row (-1: no penalties, table full, or sequence already
+        finished), with every live row holding exactly the histogram of its
+        sequence's history. This is the only place that takes slots. A
+        finished sequence can still be sampled for (the pipelined chain
+        launches its next step before the stop check of the last one); its
+        slot is gone, its token will be discarded, and it must not get a
+        slot that nothing would release."""
+        from fusioninfer_amd import ops
+
+        slots = []
+        for s in seqs:
+            slot = -1
+            if _has_penalties(s.sampling) and not s.is_finished():
+                slot = self.acquire(s)
+            slots.append(slot)
+            if slot < 0:
+                continue
+            n = len(s.all_token_ids)
+            if self._counted_len[slot] == n:
+                continue
+            if self.counts is None:
+                self.counts = torch.zeros(
+                    self.num_slots, vocab_size, dtype=torch.int32,
+                    device=self.device,
+                )
+            self.counts[slot].zero_()
+            if n:
+                # one H2D copy (the history); the slot ids are a device
+                # fill
+                ops.penalty_counts_add(
+                    self.counts,
+                    torch.full((n,), slot, dtype=torch.int32,
+                               device=self.device),
+                    torch.tensor(s.all_token_ids, dtype=torch.int64).to(
+                        self.device),
+                )
+            self._counted_len[slot] = n
+            self.num_rebuilds += 1
+        return slots
+
+    def add_sampled(self, slots: List[int], slot_ids: torch.Tensor,
+                    sampled: torch.Tensor) -> None:
+        """Count this step's sampled ids ([T] int64, on the device) into
+        the live rows; slot_ids is `slots` as a device int32 tensor."""
+        from fusioninfer_amd import ops
+
+        ops.penalty_counts_add(self.counts, slot_ids, sampled)
+        for slot in slots:
+            if slot >= 0:
+                self._counted_len[slot] += 1
+
+
 class Sampler:
     def __init__(self, seed: int = 0, device: str = "cpu",
-                 backend: str = "torch"):
+                 backend: str = "torch", penalty_slots: int = 64,
+                 device_penalties: bool = True):
         if backend not in BACKENDS:
             raise ValueError(
                 f"sampler backend must be one of {BACKENDS}, got {backend!r}"
@@ -35,10 +159,35 @@ class Sampler:
         self.base_seed = seed
         self.backend = backend
         self.num_unseeded_draws = 0  # fused backend: running Philox offset
+        # fused backend: penalties from device-resident histograms
+        self.penalty_table = None
+        if backend == "fused" and device_penalties and penalty_slots > 0:
+            self.penalty_table = PenaltyTable(penalty_slots, device)
         self.generator = None
         if device != "cpu":
             self.generator = torch.Generator(device=device)
             self.generator.manual_seed(seed)
+
+    def penalty_slot_available(self, seq: Sequence) -> bool:
+        """True when the sequence's penalties can run from the device
+        table: it owns a slot, or one is free. Takes nothing."""
+        t = self.penalty_table
+        return t is not None and (t.slot_of(seq) >= 0 or bool(t._free))
+
+    def penalty_slots_cover(self, seqs: List[Sequence]) -> bool:
+        """True when every penalised sequence of the batch that has no slot
+        yet can get one at the next sample(). Takes nothing."""
+        t = self.penalty_table
+        need = sum(
+            1 for s in seqs
+            if _has_penalties(s.sampling)
+            and (t is None or t.slot_of(s) < 0)
+        )
+        return need == 0 or (t is not None and need <= len(t._free))
+
+    def release_penalty_slot(self, seq: Sequence) -> None:
+        if self.penalty_table is not None:
+            self.penalty_table.release(seq)
 
     def _apply_penalties(self, logits: torch.Tensor, seqs: List[Sequence]):
         """repetition / presence / frequency penalties on already-emitted
@@ -71,9 +220,16 @@ class Sampler:
 
     def sample(self, logits: torch.Tensor, seqs: List[Sequence]) -> torch.Tensor:
         """logits: [S, V] fp32; returns [S] int64 token ids."""
-        logits = self._apply_penalties(logits, seqs)
         if self.backend == "fused":
-            return self._sample_fused(logits, seqs)
+            slots = None
+            if self.penalty_table is not None and any(
+                _has_penalties(s.sampling) for s in seqs
+            ):
+                slots = self.penalty_table.sync(seqs, logits.shape[-1])
+            if slots is None:
+                logits = self._apply_penalties(logits, seqs)
+            return self._sample_fused(logits, seqs, slots)
+        logits = self._apply_penalties(logits, seqs)
         greedy = logits.argmax(dim=-1)
         # host-side check: avoids a device sync on the (common) all-greedy
         # decode step
@@ -158,16 +314,26 @@ class Sampler:
             sampled[rows] = draw
         return sampled
 
-    def _sample_fused(self, logits: torch.Tensor, seqs: List[Sequence]):
+    def _sample_fused(self, logits: torch.Tensor, seqs: List[Sequence],
+                      slots=None):
         """One ops.sample_tokens call for the whole mixed batch. The per-row
         parameters are laid out in one host buffer of 8 int32 words per row
         (temperature | top_k | top_p | min_p | rng as 2 x int64) and reach
         the device in a single copy. Seeded rows draw at (seed,
         len(output_token_ids)), unseeded rows at (engine seed, 2^62 +
-        running counter): a token depends only on its row and that pair."""
+        running counter): a token depends only on its row and that pair.
+
+        `slots` (PenaltyTable.sync) switches the penalties to the device:
+        the same buffer then carries 5 more words per row (rp | 1/rp |
+        presence | frequency as [T, 4] fp32, then the slot ids), one
+        ops.apply_penalties runs before the draw and one
+        ops.penalty_counts_add after it. Penalised rows that got no slot
+        take the host _apply_penalties, row by row."""
         from fusioninfer_amd import ops
 
         T = len(seqs)
+        live = slots is not None and any(slot >= 0 for slot in slots)
+        words = 13 if live else 8
         temps, ks, ps, mps, rng = [], [], [], [], []
         for s in seqs:
             sp = s.sampling
@@ -185,22 +351,45 @@ class Sampler:
                     _as_i64(_UNSEEDED_OFFSET_BASE + self.num_unseeded_draws),
                 ))
                 self.num_unseeded_draws += 1
-        host = torch.empty(8 * T, dtype=torch.int32)
+        host = torch.empty(words * T, dtype=torch.int32)
         host[:T].view(torch.float32).copy_(torch.tensor(temps))
         host[T:2 * T].copy_(torch.tensor(ks, dtype=torch.int32))
         host[2 * T:3 * T].view(torch.float32).copy_(torch.tensor(ps))
         host[3 * T:4 * T].view(torch.float32).copy_(torch.tensor(mps))
-        host[4 * T:].view(torch.int64).copy_(
+        host[4 * T:8 * T].view(torch.int64).copy_(
             torch.tensor(rng, dtype=torch.int64).flatten()
         )
+        if live:
+            host[8 * T:12 * T].view(torch.float32).copy_(torch.tensor(
+                [penalty_params(s.sampling) for s in seqs],
+                dtype=torch.float32,
+            ).flatten())
+            host[12 * T:].copy_(torch.tensor(slots, dtype=torch.int32))
         dev = host.to(logits.device)
         if logits.dtype != torch.float32:
             logits = logits.float()
-        return ops.sample_tokens(
-            logits.contiguous(),
+        logits = logits.contiguous()
+        if slots is not None:
+            for i, s in enumerate(seqs):
+                # a finished sequence's token is discarded: no host sync
+                # for it either
+                if (slots[i] < 0 and _has_penalties(s.sampling)
+                        and not s.is_finished()):
+                    self._apply_penalties(logits[i:i + 1], [s])
+        if live:
+            slot_ids = dev[12 * T:]
+            ops.apply_penalties(
+                logits, self.penalty_table.counts, slot_ids,
+                dev[8 * T:12 * T].view(torch.float32).view(T, 4),
+            )
+        sampled = ops.sample_tokens(
+            logits,
             dev[:T].view(torch.float32),
             dev[T:2 * T],
             dev[2 * T:3 * T].view(torch.float32),
             dev[3 * T:4 * T].view(torch.float32),
-            dev[4 * T:].view(torch.int64).view(T, 2),
+            dev[4 * T:8 * T].view(torch.int64).view(T, 2),
         )
+        if live:
+            self.penalty_table.add_sampled(slots, slot_ids, sampled)
+        return sampled

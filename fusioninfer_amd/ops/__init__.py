@@ -610,4 +610,117 @@ def sample_tokens(logits, temperature, top_k, top_p, min_p, rng):
     return ref.sample_tokens(logits, temperature, top_k, top_p, min_p, rng)
 
 
+# ---------------------------------------------------------------- penalties
+
+PENALTY_MAX_ROWS = 65535  # kernel contract: T is a grid extent
+
+
+def _check_penalty_counts(op: str, counts) -> None:
+    if (counts.dim() != 2 or counts.dtype != torch.int32
+            or counts.shape[0] < 1 or counts.shape[1] < 1
+            or not counts.is_contiguous()):
+        raise ValueError(
+            f"{op}: counts must be a contiguous [S >= 1, V >= 1] int32 "
+            f"tensor, got {counts.dtype} {tuple(counts.shape)}"
+        )
+
+
+def apply_penalties(logits, counts, slot_ids, params):
+    """Repetition / presence / frequency penalties, in place on logits.
+
+    logits [T, V] fp32 contiguous, counts [S, V] int32 (row s = token
+    histogram of the sequence that owns slot s), slot_ids [T] int32,
+    params [T, 4] fp32 = (rp, inv_rp, presence, frequency) per row, with
+    inv_rp = fp32(1 / rp), the quotient taken in double
+    (engine.sampler.penalty_params). For a row with s = slot_ids[t] in
+    [0, S) and every v with c = counts[s, v] > 0:
+
+        x = x * inv_rp if x > 0 else x * rp     (rp != 1)
+        x = x - presence                        (presence != 0)
+        x = x - frequency * float(c)            (frequency != 0)
+
+    each step rounded to fp32, the operation sequence of
+    Sampler._apply_penalties (with the torch build this was tested on, the
+    GPU division by a scalar multiplies by that reciprocal; see
+    penalty_params). Rows with a slot outside [0, S) (canonically
+    -1) and elements with count 0 are left bit-for-bit untouched. One
+    launch, static grid, no host sync. Shape or dtype mismatch raises
+    ValueError. On the CPU this runs the torch ops of the sampler."""
+    if logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1:
+        raise ValueError(
+            f"apply_penalties: logits must be [T >= 1, V >= 1], got "
+            f"{tuple(logits.shape)}"
+        )
+    T, V = logits.shape
+    if logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise ValueError(
+            "apply_penalties: logits must be contiguous fp32 (the op works "
+            f"in place), got {logits.dtype} strides {logits.stride()}"
+        )
+    if T > PENALTY_MAX_ROWS or V >= 1 << 30:
+        raise ValueError(
+            f"apply_penalties: need T <= {PENALTY_MAX_ROWS} and V < 2^30, "
+            f"got T={T} V={V}"
+        )
+    _check_penalty_counts("apply_penalties", counts)
+    if counts.shape[1] != V:
+        raise ValueError(
+            f"apply_penalties: counts has {counts.shape[1]} columns, logits "
+            f"{V}"
+        )
+    for name, t, dtype, shape in (
+        ("slot_ids", slot_ids, torch.int32, (T,)),
+        ("params", params, torch.float32, (T, 4)),
+    ):
+        if t.dtype != dtype or tuple(t.shape) != shape:
+            raise ValueError(
+                f"apply_penalties: {name} must be {dtype} {shape}, got "
+                f"{t.dtype} {tuple(t.shape)}"
+            )
+    for name, t in (("counts", counts), ("slot_ids", slot_ids),
+                    ("params", params)):
+        if t.device != logits.device:
+            raise ValueError(f"apply_penalties: {name} is on {t.device}, "
+                             f"logits on {logits.device}")
+    if logits.is_cuda:
+        _require_native()
+        _C.apply_penalties(logits, counts, slot_ids.contiguous(),
+                           params.contiguous())
+        return logits
+    return ref.apply_penalties(logits, counts, slot_ids, params)
+
+
+def penalty_counts_add(counts, slot_ids, token_ids):
+    """counts[slot_ids[i], token_ids[i]] += 1 for every i, in place.
+
+    counts [S, V] int32, slot_ids [N] int32, token_ids [N] int64. An entry
+    whose slot is outside [0, S) or whose token is outside [0, V) is
+    skipped (never used as an index). Integer atomics: duplicate tokens and
+    slots count exactly, in any order. One launch, no host sync. Shape or
+    dtype mismatch raises ValueError."""
+    _check_penalty_counts("penalty_counts_add", counts)
+    if counts.shape[1] >= 1 << 30:
+        raise ValueError("penalty_counts_add: need V < 2^30")
+    N = slot_ids.numel()
+    if (slot_ids.dim() != 1 or N < 1 or slot_ids.dtype != torch.int32
+            or token_ids.dtype != torch.int64
+            or tuple(token_ids.shape) != (N,)):
+        raise ValueError(
+            "penalty_counts_add: slot_ids must be int32 [N >= 1] and "
+            f"token_ids int64 [N], got {slot_ids.dtype} "
+            f"{tuple(slot_ids.shape)} and {token_ids.dtype} "
+            f"{tuple(token_ids.shape)}"
+        )
+    for name, t in (("slot_ids", slot_ids), ("token_ids", token_ids)):
+        if t.device != counts.device:
+            raise ValueError(f"penalty_counts_add: {name} is on {t.device}, "
+                             f"counts on {counts.device}")
+    if counts.is_cuda:
+        _require_native()
+        _C.penalty_counts_add(counts, slot_ids.contiguous(),
+                              token_ids.contiguous())
+        return counts
+    return ref.penalty_counts_add(counts, slot_ids, token_ids)
+
+
 compute_cos_sin_cache = ref.compute_cos_sin_cache

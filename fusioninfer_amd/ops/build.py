@@ -29,6 +29,7 @@ SOURCES = [
     "moe_gemm.hip",
     "lora.hip",
     "sampling.hip",
+    "penalties.hip",
 ]
 
 

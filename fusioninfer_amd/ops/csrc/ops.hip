@@ -56,6 +56,10 @@ void launch_lora_apply(u16*, u16*, const u16*, const int*, const u16*,
 void launch_sample_tokens(int64_t*, const float*, const float*, const int*,
                           const float*, const float*, const int64_t*, int,
                           int, hipStream_t);
+void launch_apply_penalties(float*, const int*, const int*, const float*, int,
+                            int, int, hipStream_t);
+void launch_penalty_counts_add(int*, const int*, const int64_t*, int, int,
+                               int, hipStream_t);
 
 }  // namespace fi
 
@@ -616,6 +620,61 @@ void sample_tokens(at::Tensor out, at::Tensor logits, at::Tensor temperature,
       current_stream());
 }
 
+void apply_penalties(at::Tensor logits, at::Tensor counts,
+                     at::Tensor slot_ids, at::Tensor params) {
+  TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == at::kFloat &&
+              logits.is_contiguous() && logits.dim() == 2,
+              "apply_penalties: logits must be a contiguous [T, V] fp32 GPU "
+              "tensor");
+  const int64_t T = logits.size(0);
+  const int64_t V = logits.size(1);
+  // T is the grid's y extent
+  TORCH_CHECK(T >= 1 && T <= 65535 && V >= 1 && V < (1LL << 30),
+              "apply_penalties: need 1 <= T <= 65535 and 1 <= V < 2^30");
+  TORCH_CHECK(counts.is_cuda() && counts.scalar_type() == at::kInt &&
+              counts.is_contiguous() && counts.dim() == 2 &&
+              counts.size(0) >= 1 && counts.size(0) < (1LL << 31) &&
+              counts.size(1) == V,
+              "apply_penalties: counts must be a contiguous [S >= 1, V] "
+              "int32 GPU tensor");
+  TORCH_CHECK(slot_ids.is_cuda() && slot_ids.scalar_type() == at::kInt &&
+              slot_ids.is_contiguous() && slot_ids.numel() == T,
+              "apply_penalties: bad slot_ids");
+  TORCH_CHECK(params.is_cuda() && params.scalar_type() == at::kFloat &&
+              params.is_contiguous() && params.numel() == 4 * T,
+              "apply_penalties: bad params");
+  fi::launch_apply_penalties(
+      logits.data_ptr<float>(), counts.data_ptr<int>(),
+      slot_ids.data_ptr<int>(), params.data_ptr<float>(),
+      static_cast<int>(T), static_cast<int>(V),
+      static_cast<int>(counts.size(0)), current_stream());
+}
+
+void penalty_counts_add(at::Tensor counts, at::Tensor slot_ids,
+                        at::Tensor token_ids) {
+  TORCH_CHECK(counts.is_cuda() && counts.scalar_type() == at::kInt &&
+              counts.is_contiguous() && counts.dim() == 2 &&
+              counts.size(0) >= 1 && counts.size(0) < (1LL << 31) &&
+              counts.size(1) >= 1 && counts.size(1) < (1LL << 30),
+              "penalty_counts_add: counts must be a contiguous [S >= 1, "
+              "1 <= V < 2^30] int32 GPU tensor");
+  const int64_t N = slot_ids.numel();
+  TORCH_CHECK(N >= 1 && N < (1LL << 31) - 256,
+              "penalty_counts_add: need 1 <= N < 2^31 - 256");
+  TORCH_CHECK(slot_ids.is_cuda() && slot_ids.scalar_type() == at::kInt &&
+              slot_ids.is_contiguous() && slot_ids.dim() == 1,
+              "penalty_counts_add: bad slot_ids");
+  TORCH_CHECK(token_ids.is_cuda() && token_ids.scalar_type() == at::kLong &&
+              token_ids.is_contiguous() && token_ids.dim() == 1 &&
+              token_ids.numel() == N,
+              "penalty_counts_add: bad token_ids");
+  fi::launch_penalty_counts_add(
+      counts.data_ptr<int>(), slot_ids.data_ptr<int>(),
+      token_ids.data_ptr<int64_t>(), static_cast<int>(N),
+      static_cast<int>(counts.size(1)), static_cast<int>(counts.size(0)),
+      current_stream());
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -660,4 +719,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sample_tokens", &sample_tokens,
         "fused temperature / top-k / top-p / min-p sampling with a "
         "counter-based (Philox4x32-10) draw, one workgroup per row");
+  m.def("apply_penalties", &apply_penalties,
+        "repetition / presence / frequency penalties from a per-slot token "
+        "histogram (in-place on logits)");
+  m.def("penalty_counts_add", &penalty_counts_add,
+        "counts[slot_ids[i], token_ids[i]] += 1 (integer atomics)");
 }

@@ -524,3 +524,45 @@ def sample_tokens(logits, temperature, top_k, top_p, min_p, rng,
     if return_margin:
         return out, torch.tensor(margins, dtype=torch.float64)
     return out
+
+
+# ---------------------------------------------------------------- penalties
+
+def apply_penalties(logits, counts, slot_ids, params):
+    """Reference of the penalty kernel, in place on logits [T, V] fp32: the
+    torch ops of Sampler._apply_penalties, with the row's (token, count)
+    pairs read from counts[slot_ids[t]] ([S, V] int32) instead of a
+    unique() over the history, and params[t] = (rp, inv_rp, presence,
+    frequency) as fp32. Rows whose slot is outside [0, S) and elements
+    whose count is 0 are left untouched. The division is torch's own (the
+    GPU kernel multiplies by inv_rp, which matched torch's GPU division by
+    a scalar on the build it was tested with)."""
+    S = counts.shape[0]
+    for t, slot in enumerate(slot_ids.tolist()):
+        if slot < 0 or slot >= S:
+            continue
+        rp, _, presence, frequency = params[t].tolist()
+        uniq = counts[slot].nonzero().flatten()
+        c = counts[slot][uniq]
+        row = logits[t]
+        if rp != 1.0:
+            vals = row[uniq]
+            row[uniq] = torch.where(vals > 0, vals / rp, vals * rp)
+        if presence != 0.0:
+            row[uniq] -= presence
+        if frequency != 0.0:
+            row[uniq] -= frequency * c.to(row.dtype)
+    return logits
+
+
+def penalty_counts_add(counts, slot_ids, token_ids):
+    """counts[slot_ids[i], token_ids[i]] += 1; entries whose slot is outside
+    [0, S) or whose token is outside [0, V) are skipped."""
+    S, V = counts.shape
+    slots = slot_ids.long()
+    ok = (slots >= 0) & (slots < S) & (token_ids >= 0) & (token_ids < V)
+    flat = slots[ok] * V + token_ids[ok]
+    counts.view(-1).index_add_(
+        0, flat, torch.ones_like(flat, dtype=counts.dtype)
+    )
+    return counts

@@ -42,6 +42,14 @@ def parse_args(argv=None):
                    default="torch",
                    help="fused: one HIP sampling launch per step "
                         "(top-k/top-p/min-p, counter-based seeded draws)")
+    p.add_argument("--penalty-slots", type=int, default=64,
+                   help="fused sampler: sequences whose repetition / "
+                        "presence / frequency penalties run from a "
+                        "device-resident token histogram (vocab x 4 bytes "
+                        "each, allocated on first use); further penalised "
+                        "sequences take the host path")
+    p.add_argument("--no-device-penalties", action="store_true",
+                   help="fused sampler: keep all penalties on the host path")
     p.add_argument("--kv-cache-dtype", choices=["auto", "fp8"], default="auto")
     p.add_argument("--swap-space", type=float, default=0.0,
                    help="GiB of CPU swap for preempted sequences (0=recompute)")
@@ -150,6 +158,8 @@ def build_engine_config(args):
         max_lora_rank=args.max_lora_rank,
         enforce_eager=args.enforce_eager,
         sampler_backend=args.sampler_backend,
+        penalty_slots=args.penalty_slots,
+        device_penalties=not args.no_device_penalties,
     )
 
 

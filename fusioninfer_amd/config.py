@@ -159,4 +159,10 @@ class EngineConfig:
     # the A/B switch back to the host path for all of them.
     penalty_slots: int = 64
     device_penalties: bool = True
+    # Fused backend only: `logprobs` of up to 32 top entries come from one
+    # HIP token_logprobs launch per step and ride to the host with the
+    # sampled ids, so such sequences stay on the pipelined-decode chain.
+    # Requests asking for more take the host path. device_logprobs=False
+    # is the A/B switch back to the host path for all of them.
+    device_logprobs: bool = True
     enforce_eager: bool = False            # True disables hipGraph decode capture

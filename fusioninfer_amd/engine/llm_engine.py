@@ -17,7 +17,7 @@ import torch
 from fusioninfer_amd.config import EngineConfig
 from fusioninfer_amd.engine.block_manager import BlockManager
 from fusioninfer_amd.engine.model_runner import ModelRunner
-from fusioninfer_amd.engine.sampler import Sampler
+from fusioninfer_amd.engine.sampler import Sampler, device_logprobs_top
 from fusioninfer_amd.engine.scheduler import Scheduler
 from fusioninfer_amd.engine.sequence import SamplingParams, Sequence, SeqStatus
 
@@ -88,7 +88,8 @@ class LLMEngine:
         self.sampler = Sampler(cfg.seed, device,
                                backend=cfg.sampler_backend,
                                penalty_slots=cfg.penalty_slots,
-                               device_penalties=cfg.device_penalties)
+                               device_penalties=cfg.device_penalties,
+                               device_logprobs=cfg.device_logprobs)
         from fusioninfer_amd.engine.spec_decode import build_proposer
 
         if (cfg.speculative is not None
@@ -673,12 +674,16 @@ class LLMEngine:
         """Pipeline-eligible: nothing about next-step sampling may depend
         on THIS step's token value on the host (guided masks, penalties
         over emitted tokens unless their histogram lives on the device)
-        and nothing extra is read back (logprobs)."""
+        and nothing extra is read back beyond what rides on the pinned
+        copy of the sampled ids (logprobs of up to LOGPROBS_MAX_TOP
+        entries from the fused backend's kernel)."""
         sp = s.sampling
         return (
             sp.guided is None
             and not sp.logit_bias
-            and sp.logprobs is None
+            and (sp.logprobs is None
+                 or (self.sampler.device_logprobs
+                     and device_logprobs_top(sp) >= 0))
             and sp.prompt_logprobs is None
             and s.lora_name is None
             and (
@@ -701,20 +706,29 @@ class LLMEngine:
     def _stash_pending(self, seqs, logits) -> None:
         """Sample on-device and record the in-flight step: the sampled
         ids tensor feeds the next launch device-to-device; the pinned
-        host copy (awaited via the event at drain time) feeds emission."""
+        host copy (awaited via the event at drain time) feeds emission.
+        Device-side logprobs of the step travel the same way: one more
+        pinned copy in front of the same event."""
         logits_f = logits.float()
-        sampled = self.sampler.sample(logits_f, seqs)
+        sampled, lp = self.sampler.sample_with_logprobs(logits_f, seqs)
+        lp_host = None if lp is None else lp.buf
         if sampled.is_cuda:
             host = torch.empty(
                 sampled.shape, dtype=sampled.dtype, pin_memory=True
             )
             host.copy_(sampled, non_blocking=True)
+            if lp is not None:
+                lp_host = torch.empty(
+                    lp.buf.shape, dtype=lp.buf.dtype, pin_memory=True
+                )
+                lp_host.copy_(lp.buf, non_blocking=True)
             ev = torch.cuda.Event()
             ev.record()
         else:
             host, ev = sampled, None
         self._pending = {
             "seqs": list(seqs), "sampled": sampled, "host": host, "event": ev,
+            "lp": lp, "lp_host": lp_host,
         }
 
     def _drain_pending(self) -> List[RequestOutput]:
@@ -728,11 +742,17 @@ class LLMEngine:
         if p["event"] is not None:
             p["event"].synchronize()
         toks = p["host"].tolist()
-        return [
-            self._emit_tokens(s, [t])
-            for s, t in zip(p["seqs"], toks)
-            if not s.is_finished()
-        ]
+        entries = None
+        if p["lp"] is not None:
+            entries = p["lp"].entries(p["lp_host"])
+        outputs = []
+        for i, (s, t) in enumerate(zip(p["seqs"], toks)):
+            if s.is_finished():
+                continue  # neither the late token nor its logprobs entry
+            if entries is not None and entries[i] is not None:
+                s.logprobs.append(entries[i])
+            outputs.append(self._emit_tokens(s, [t]))
+        return outputs
 
     def _try_continue_async(self):
         """Continue the pipelined pure-decode chain: launch step N+1
@@ -839,11 +859,23 @@ class LLMEngine:
         if len(keep) < len(sample_seqs):
             sample_seqs = [sample_seqs[i] for i in keep]
             logits_f = logits_f[keep]
-        next_tokens = self.sampler.sample(logits_f, sample_seqs).tolist()
-        # optional logprobs for requests that asked
+        # fused backend with device_logprobs: one kernel and one readback
+        # serve every row that asks for at most LOGPROBS_MAX_TOP entries
+        sampled, dev_lp = self.sampler.sample_with_logprobs(
+            logits_f, sample_seqs
+        )
+        next_tokens = sampled.tolist()
+        served = set()
+        if dev_lp is not None:
+            entries = dev_lp.entries(dev_lp.buf.cpu())
+            for i, e in enumerate(entries):
+                if e is not None:
+                    sample_seqs[i].logprobs.append(e)
+                    served.add(i)
+        # the others that asked: log_softmax + topk on the host
         lp_rows = [
             i for i, s in enumerate(sample_seqs)
-            if s.sampling.logprobs is not None
+            if s.sampling.logprobs is not None and i not in served
         ]
         if lp_rows:
             lp = torch.log_softmax(logits_f[lp_rows], dim=-1)

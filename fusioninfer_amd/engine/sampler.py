@@ -47,6 +47,56 @@ def penalty_params(sp):
             sp.presence_penalty, sp.frequency_penalty)
 
 
+def device_logprobs_top(sp) -> int:
+    """num_top of ops.token_logprobs for one request: the number of top
+    entries when the kernel can serve it (at most ops.LOGPROBS_MAX_TOP),
+    -1 when the request has no logprobs or asks for more."""
+    from fusioninfer_amd import ops
+
+    if sp.logprobs is None:
+        return -1
+    k = max(int(sp.logprobs), 0)
+    return k if k <= ops.LOGPROBS_MAX_TOP else -1
+
+
+class DeviceLogprobs:
+    """ops.token_logprobs outputs of one step in ONE int32 buffer, so that
+    a single copy brings them to the host: chosen [T] fp32 | top_ids [T, W]
+    int32 | top_lp [T, W] fp32. num_top is the host list the kernel ran
+    with; rows with -1 were skipped and hold nothing."""
+
+    def __init__(self, buf: torch.Tensor, num_top: List[int], width: int):
+        self.buf = buf
+        self.num_top = num_top
+        self.width = width
+
+    @staticmethod
+    def sections(buf: torch.Tensor, T: int, W: int):
+        return (
+            buf[:T].view(torch.float32),
+            buf[T:T + T * W].view(T, W),
+            buf[T + T * W:].view(torch.float32).view(T, W),
+        )
+
+    def entries(self, host_buf: torch.Tensor):
+        """host_buf: self.buf (or a host copy of it) once its contents are
+        there. One (chosen, {id: logprob}) per row, None for skipped
+        rows; the format of Sequence.logprobs."""
+        T, W = len(self.num_top), self.width
+        chosen, ids, vals = (
+            x.tolist() for x in self.sections(host_buf, T, W)
+        )
+        out = []
+        for i, k in enumerate(self.num_top):
+            if k < 0:
+                out.append(None)
+                continue
+            out.append((chosen[i], {
+                t: v for t, v in zip(ids[i][:k], vals[i][:k]) if t >= 0
+            }))
+        return out
+
+
 class PenaltyTable:
     """Device-resident token histograms for penalised sequences (the slot
     idea of lora.LoRASlots): counts [num_slots, V] int32, row = slot. The
@@ -150,7 +200,8 @@ class PenaltyTable:
 class Sampler:
     def __init__(self, seed: int = 0, device: str = "cpu",
                  backend: str = "torch", penalty_slots: int = 64,
-                 device_penalties: bool = True):
+                 device_penalties: bool = True,
+                 device_logprobs: bool = True):
         if backend not in BACKENDS:
             raise ValueError(
                 f"sampler backend must be one of {BACKENDS}, got {backend!r}"
@@ -163,6 +214,8 @@ class Sampler:
         self.penalty_table = None
         if backend == "fused" and device_penalties and penalty_slots > 0:
             self.penalty_table = PenaltyTable(penalty_slots, device)
+        # fused backend: logprobs from ops.token_logprobs, no host loop
+        self.device_logprobs = backend == "fused" and device_logprobs
         self.generator = None
         if device != "cpu":
             self.generator = torch.Generator(device=device)
@@ -218,17 +271,38 @@ class Sampler:
                 row[uniq] -= sp.frequency_penalty * counts.to(row.dtype)
         return logits
 
+    def sample_with_logprobs(self, logits: torch.Tensor,
+                             seqs: List[Sequence]):
+        """sample() plus, with device_logprobs, one ops.token_logprobs launch
+        on the logits the draw saw (after logit_bias, guided masks and
+        penalties, before temperature) for the rows device_logprobs_top()
+        serves. Returns (token ids, DeviceLogprobs or None); None when no
+        row is served, and then nothing is launched or allocated. The
+        tokens are those of sample()."""
+        num_top = None
+        if self.device_logprobs:
+            tops = [device_logprobs_top(s.sampling) for s in seqs]
+            if any(k >= 0 for k in tops):
+                num_top = tops
+        if num_top is None:
+            return self.sample(logits, seqs), None
+        return self._sample(logits, seqs, num_top)
+
+    def _sample(self, logits, seqs, num_top=None):
+        """The fused backend's step: (token ids, DeviceLogprobs or None)."""
+        slots = None
+        if self.penalty_table is not None and any(
+            _has_penalties(s.sampling) for s in seqs
+        ):
+            slots = self.penalty_table.sync(seqs, logits.shape[-1])
+        if slots is None:
+            logits = self._apply_penalties(logits, seqs)
+        return self._sample_fused(logits, seqs, slots, num_top)
+
     def sample(self, logits: torch.Tensor, seqs: List[Sequence]) -> torch.Tensor:
         """logits: [S, V] fp32; returns [S] int64 token ids."""
         if self.backend == "fused":
-            slots = None
-            if self.penalty_table is not None and any(
-                _has_penalties(s.sampling) for s in seqs
-            ):
-                slots = self.penalty_table.sync(seqs, logits.shape[-1])
-            if slots is None:
-                logits = self._apply_penalties(logits, seqs)
-            return self._sample_fused(logits, seqs, slots)
+            return self._sample(logits, seqs)[0]
         logits = self._apply_penalties(logits, seqs)
         greedy = logits.argmax(dim=-1)
         # host-side check: avoids a device sync on the (common) all-greedy
@@ -315,7 +389,7 @@ class Sampler:
         return sampled
 
     def _sample_fused(self, logits: torch.Tensor, seqs: List[Sequence],
-                      slots=None):
+                      slots=None, num_top=None):
         """One ops.sample_tokens call for the whole mixed batch. The per-row
         parameters are laid out in one host buffer of 8 int32 words per row
         (temperature | top_k | top_p | min_p | rng as 2 x int64) and reach
@@ -328,12 +402,18 @@ class Sampler:
         presence | frequency as [T, 4] fp32, then the slot ids), one
         ops.apply_penalties runs before the draw and one
         ops.penalty_counts_add after it. Penalised rows that got no slot
-        take the host _apply_penalties, row by row."""
+        take the host _apply_penalties, row by row.
+
+        `num_top` (one int per row, see device_logprobs_top) adds one more
+        word per row at the end of the buffer and one ops.token_logprobs
+        launch after the draw, on the same logits and the sampled ids.
+        Returns (sampled ids, DeviceLogprobs or None)."""
         from fusioninfer_amd import ops
 
         T = len(seqs)
         live = slots is not None and any(slot >= 0 for slot in slots)
-        words = 13 if live else 8
+        pen_words = 13 if live else 8
+        words = pen_words + (1 if num_top is not None else 0)
         temps, ks, ps, mps, rng = [], [], [], [], []
         for s in seqs:
             sp = s.sampling
@@ -364,7 +444,10 @@ class Sampler:
                 [penalty_params(s.sampling) for s in seqs],
                 dtype=torch.float32,
             ).flatten())
-            host[12 * T:].copy_(torch.tensor(slots, dtype=torch.int32))
+            host[12 * T:13 * T].copy_(torch.tensor(slots, dtype=torch.int32))
+        if num_top is not None:
+            host[pen_words * T:].copy_(
+                torch.tensor(num_top, dtype=torch.int32))
         dev = host.to(logits.device)
         if logits.dtype != torch.float32:
             logits = logits.float()
@@ -377,7 +460,7 @@ class Sampler:
                         and not s.is_finished()):
                     self._apply_penalties(logits[i:i + 1], [s])
         if live:
-            slot_ids = dev[12 * T:]
+            slot_ids = dev[12 * T:13 * T]
             ops.apply_penalties(
                 logits, self.penalty_table.counts, slot_ids,
                 dev[8 * T:12 * T].view(torch.float32).view(T, 4),
@@ -392,4 +475,14 @@ class Sampler:
         )
         if live:
             self.penalty_table.add_sampled(slots, slot_ids, sampled)
-        return sampled
+        if num_top is None:
+            return sampled, None
+        # as wide as the widest request of the step: less to copy back
+        W = max(max(num_top), 1)
+        buf = torch.empty(T * (1 + 2 * W), dtype=torch.int32,
+                          device=logits.device)
+        ops.token_logprobs(
+            logits, sampled, dev[pen_words * T:],
+            out=DeviceLogprobs.sections(buf, T, W),
+        )
+        return sampled, DeviceLogprobs(buf, num_top, W)

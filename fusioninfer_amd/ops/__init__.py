@@ -610,6 +610,96 @@ def sample_tokens(logits, temperature, top_k, top_p, min_p, rng):
     return ref.sample_tokens(logits, temperature, top_k, top_p, min_p, rng)
 
 
+# ---------------------------------------------------------------- logprobs
+
+LOGPROBS_MAX_TOP = 32  # kernel contract: the top list lives in LDS
+
+
+def token_logprobs(logits, token_ids, num_top, width=LOGPROBS_MAX_TOP,
+                   out=None):
+    """Per row: the log-softmax value of one token and the top-k (id,
+    logprob) pairs, with no host involvement.
+
+    logits [T, V] fp32 contiguous, token_ids [T] int64, num_top [T] int32.
+    Returns (chosen [T] fp32, top_ids [T, W] int32, top_lp [T, W] fp32)
+    with W = width, 1 <= W <= LOGPROBS_MAX_TOP. Row t with num_top[t] < 0
+    is skipped: its logits are not read and its outputs not written. For
+    the others, with lp(i) = x_i - (m + log(sum(exp(x - m)))), m = max x:
+
+        chosen[t] = lp(token_ids[t]), NaN for an id outside [0, V) (the id
+            is range-checked before it is used as an index)
+        k = min(num_top[t], W, V)
+        top_ids[t, :k] = indices of the k largest logits in the order
+            (logit descending, index ascending), -0.0 equal to +0.0: an
+            exact function of the inputs
+        top_lp[t, :k] = their logprobs; columns >= k get id -1 and -inf
+
+    -inf logits are ordinary values (lp = -inf); a row without a finite
+    entry gives -inf everywhere. NaN / +inf logits are outside the
+    contract. The sum of exponentials runs in a fixed order: a row's bits
+    depend only on the row and V.
+
+    out = (chosen, top_ids, top_lp) writes into existing tensors, e.g.
+    views of one buffer; `width` is then taken from top_ids. Without out=
+    the outputs of skipped rows are uninitialised. One launch, static grid,
+    no host sync. Shape, dtype, device or contiguity mismatch raises
+    ValueError. On the CPU this is reference.token_logprobs."""
+    if logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1:
+        raise ValueError(
+            f"token_logprobs: logits must be [T >= 1, V >= 1], got "
+            f"{tuple(logits.shape)}"
+        )
+    T, V = logits.shape
+    if logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise ValueError(
+            "token_logprobs: logits must be contiguous fp32, got "
+            f"{logits.dtype} strides {logits.stride()}"
+        )
+    if V >= 1 << 30:
+        raise ValueError(f"token_logprobs: need V < 2^30, got {V}")
+    if out is not None:
+        if len(out) != 3 or out[1].dim() != 2:
+            raise ValueError(
+                "token_logprobs: out must be (chosen [T], top_ids [T, W], "
+                "top_lp [T, W])"
+            )
+        width = out[1].shape[1]
+    if not 1 <= width <= LOGPROBS_MAX_TOP:
+        raise ValueError(
+            f"token_logprobs: need 1 <= width <= {LOGPROBS_MAX_TOP}, got "
+            f"{width}"
+        )
+    if out is None:
+        out = (
+            torch.empty(T, dtype=torch.float32, device=logits.device),
+            torch.empty(T, width, dtype=torch.int32, device=logits.device),
+            torch.empty(T, width, dtype=torch.float32, device=logits.device),
+        )
+    for name, t, dtype, shape in (
+        ("token_ids", token_ids, torch.int64, (T,)),
+        ("num_top", num_top, torch.int32, (T,)),
+        ("chosen", out[0], torch.float32, (T,)),
+        ("top_ids", out[1], torch.int32, (T, width)),
+        ("top_lp", out[2], torch.float32, (T, width)),
+    ):
+        if t.dtype != dtype or tuple(t.shape) != shape:
+            raise ValueError(
+                f"token_logprobs: {name} must be {dtype} {shape}, got "
+                f"{t.dtype} {tuple(t.shape)}"
+            )
+        if t.device != logits.device:
+            raise ValueError(f"token_logprobs: {name} is on {t.device}, "
+                             f"logits on {logits.device}")
+        if not t.is_contiguous():
+            raise ValueError(f"token_logprobs: {name} must be contiguous, "
+                             f"got strides {t.stride()}")
+    if logits.is_cuda:
+        _require_native()
+        _C.token_logprobs(out[0], out[1], out[2], logits, token_ids, num_top)
+        return tuple(out)
+    return ref.token_logprobs(logits, token_ids, num_top, tuple(out))
+
+
 # ---------------------------------------------------------------- penalties
 
 PENALTY_MAX_ROWS = 65535  # kernel contract: T is a grid extent

@@ -56,6 +56,8 @@ void launch_lora_apply(u16*, u16*, const u16*, const int*, const u16*,
 void launch_sample_tokens(int64_t*, const float*, const float*, const int*,
                           const float*, const float*, const int64_t*, int,
                           int, hipStream_t);
+void launch_token_logprobs(float*, int*, float*, const float*, const int64_t*,
+                           const int*, int, int, int, hipStream_t);
 void launch_apply_penalties(float*, const int*, const int*, const float*, int,
                             int, int, hipStream_t);
 void launch_penalty_counts_add(int*, const int*, const int64_t*, int, int,
@@ -620,6 +622,41 @@ void sample_tokens(at::Tensor out, at::Tensor logits, at::Tensor temperature,
       current_stream());
 }
 
+void token_logprobs(at::Tensor chosen, at::Tensor top_ids, at::Tensor top_lp,
+                    at::Tensor logits, at::Tensor token_ids,
+                    at::Tensor num_top) {
+  TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == at::kFloat &&
+              logits.is_contiguous() && logits.dim() == 2,
+              "token_logprobs: logits must be a contiguous [T, V] fp32 GPU "
+              "tensor");
+  const int64_t T = logits.size(0);
+  const int64_t V = logits.size(1);
+  TORCH_CHECK(T >= 1 && T < (1LL << 31) && V >= 1 && V < (1LL << 30),
+              "token_logprobs: need 1 <= T < 2^31 and 1 <= V < 2^30");
+  TORCH_CHECK(top_ids.dim() == 2 && top_ids.size(0) == T,
+              "token_logprobs: top_ids must be [T, W]");
+  const int64_t W = top_ids.size(1);
+  // W bounds the kernel's LDS list
+  TORCH_CHECK(W >= 1 && W <= 32, "token_logprobs: need 1 <= W <= 32");
+  auto check = [&](const at::Tensor& t, at::ScalarType ty, int64_t n,
+                   const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == ty && t.is_contiguous() &&
+                    t.numel() == n,
+                "token_logprobs: bad ", name);
+  };
+  check(chosen, at::kFloat, T, "chosen");
+  check(top_ids, at::kInt, T * W, "top_ids");
+  check(top_lp, at::kFloat, T * W, "top_lp");
+  check(token_ids, at::kLong, T, "token_ids");
+  check(num_top, at::kInt, T, "num_top");
+  fi::launch_token_logprobs(
+      chosen.data_ptr<float>(), top_ids.data_ptr<int>(),
+      top_lp.data_ptr<float>(), logits.data_ptr<float>(),
+      token_ids.data_ptr<int64_t>(), num_top.data_ptr<int>(),
+      static_cast<int>(T), static_cast<int>(V), static_cast<int>(W),
+      current_stream());
+}
+
 void apply_penalties(at::Tensor logits, at::Tensor counts,
                      at::Tensor slot_ids, at::Tensor params) {
   TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == at::kFloat &&
@@ -719,6 +756,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sample_tokens", &sample_tokens,
         "fused temperature / top-k / top-p / min-p sampling with a "
         "counter-based (Philox4x32-10) draw, one workgroup per row");
+  m.def("token_logprobs", &token_logprobs,
+        "log-softmax value of one token per row plus the top-k (id, "
+        "logprob) pairs, one workgroup per row");
   m.def("apply_penalties", &apply_penalties,
         "repetition / presence / frequency penalties from a per-slot token "
         "histogram (in-place on logits)");

@@ -378,6 +378,180 @@ __global__ __launch_bounds__(kSampThreads) void sample_tokens_kernel(
   if (tid == 0) out[r_i] = bi;
 }
 
+// ---------------------------------------------------------------------------
+// token_logprobs: log-softmax value of one token per row plus the k largest
+// (id, logprob) pairs, k <= kLpMaxTop, one workgroup per row.
+//
+//   logZ = m + logf(S),  m = max x,  S = sum expf(x - m),  lp(i) = x_i - logZ
+//
+// S is a float sum in a FIXED order: per-thread partials over the thread's
+// elements in index order (the same elements on the 16 B and on the scalar
+// load path), a xor butterfly per wave, then the 16 wave sums added in wave
+// order. A row's bits depend only on the row and V.
+//
+// Top entries, ordered by (logit descending, index ascending) on the input
+// values with -0 folded into +0: the radix descent gives the k-th largest
+// key t_k; one pass appends the (fewer than k) elements above t_k to a list
+// in LDS in arrival order; a tiled index-order scan adds the lowest-index
+// elements equal to t_k until the list holds k; k threads then rank the list
+// by counting predecessors. The ids are an exact function of the inputs.
+//
+// No index is derived from data: list slots come from a bounded counter or a
+// bounded rank, output columns from a count over at most k - 1 others, and
+// the token id is range-checked before it forms an address. NaN / +inf logits
+// are outside the contract but cannot cause an out-of-bounds access.
+
+constexpr int kLpMaxTop = 32;
+
+struct LpShared {
+  int idx[kLpMaxTop];
+  float val[kLpMaxTop];
+  int n_above;
+};
+
+template <bool MAX>
+FI_DEV float block_reduce_f32(float v, SampShared& sh) {
+  const int lane = threadIdx.x % kWaveSize;
+  const int wave = threadIdx.x / kWaveSize;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const float o = __shfl_xor(v, off, kWaveSize);
+    v = MAX ? fmaxf(v, o) : v + o;
+  }
+  __syncthreads();  // readers of an earlier reduction are done
+  if (lane == 0) sh.red_val[wave] = v;
+  __syncthreads();
+  float r = sh.red_val[0];
+#pragma unroll
+  for (int i = 1; i < kSampWaves; ++i)
+    r = MAX ? fmaxf(r, sh.red_val[i]) : r + sh.red_val[i];
+  return r;
+}
+
+__global__ __launch_bounds__(kSampThreads) void token_logprobs_kernel(
+    float* __restrict__ chosen, int* __restrict__ top_ids,
+    float* __restrict__ top_lp, const float* __restrict__ logits,
+    const int64_t* __restrict__ token_ids, const int* __restrict__ num_top,
+    int V, int W, int vec_i) {
+  __shared__ SampShared sh;
+  __shared__ LpShared ls;
+  const int tid = threadIdx.x;
+  const int r_i = blockIdx.x;
+  const int want = num_top[r_i];
+  if (want < 0) return;  // skipped row: nothing read, nothing written
+  const bool vec = vec_i != 0;
+  const float* __restrict__ row = logits + static_cast<size_t>(r_i) * V;
+  const float ninf = -__builtin_inff();
+  const int width = W < kLpMaxTop ? W : kLpMaxTop;
+  int k = want < width ? want : width;
+  k = k < V ? k : V;
+
+  if (tid < kLpMaxTop) {
+    ls.idx[tid] = -1;
+    ls.val[tid] = ninf;
+  }
+  if (tid == 0) ls.n_above = 0;
+
+  // ---- log-partition
+  float part = ninf;
+  for_each_elem(row, V, vec, [&](int, float x) { part = fmaxf(part, x); });
+  const float m = block_reduce_f32<true>(part, sh);
+  const bool none_finite = !(m > ninf);
+  float logz = 0.0f;
+  if (!none_finite) {
+    part = 0.0f;
+    for_each_elem(row, V, vec, [&](int, float x) { part += expf(x - m); });
+    logz = m + logf(block_reduce_f32<false>(part, sh));
+  }
+  auto lp_of = [&](float x) { return none_finite ? ninf : x - logz; };
+
+  if (tid == 0) {
+    const int64_t tok = token_ids[r_i];
+    float c = __builtin_nanf("");
+    if (tok >= 0 && tok < static_cast<int64_t>(V)) c = lp_of(row[tok]);
+    chosen[r_i] = c;
+  }
+  // columns past k: id -1, value -inf
+  if (tid >= k && tid < W) {
+    top_ids[static_cast<size_t>(r_i) * W + tid] = -1;
+    top_lp[static_cast<size_t>(r_i) * W + tid] = ninf;
+  }
+  if (k == 0) return;
+
+  // ---- k-th largest key (temperature 1: scaled() only folds -0)
+  u64 unused;
+  const u32 tk = radix_descend<false>(row, V, vec, 1.0f, 0.0f, 0u,
+                                      static_cast<u64>(k - 1), sh, &unused);
+
+  // ---- everything above t_k, in arrival order (fewer than k elements)
+  for_each_elem(row, V, vec, [&](int i, float x) {
+    const float z = scaled(x, 1.0f);
+    if (float_key(z) > tk) {
+      const int slot = atomicAdd(&ls.n_above, 1);
+      if (slot < kLpMaxTop) {
+        ls.idx[slot] = i;
+        ls.val[slot] = z;
+      }
+    }
+  });
+  __syncthreads();
+  const int n_above = ls.n_above < k - 1 ? ls.n_above : k - 1;
+  const u64 need = static_cast<u64>(k - n_above);
+
+  // ---- the lowest-index elements equal to t_k fill the rest
+  const int ntiles = (V + kSampTile - 1) / kSampTile;
+  u64 carry = 0;
+  float4 cur = load_tile4(row, tid * kSampVec, V, vec);
+#pragma unroll 1
+  for (int tile = 0; tile < ntiles; ++tile) {
+    const int i0 = tile * kSampTile + tid * kSampVec;
+    float4 nxt = cur;
+    if (tile + 1 < ntiles) nxt = load_tile4(row, i0 + kSampTile, V, vec);
+    const float z[kSampVec] = {scaled(cur.x, 1.0f), scaled(cur.y, 1.0f),
+                               scaled(cur.z, 1.0f), scaled(cur.w, 1.0f)};
+    bool eq[kSampVec];
+    u64 s = 0;
+#pragma unroll
+    for (int j = 0; j < kSampVec; ++j) {
+      // the pad past the row end reads as -inf and may equal t_k
+      eq[j] = i0 + j < V && float_key(z[j]) == tk;
+      s += eq[j] ? 1 : 0;
+    }
+    u64 total;
+    const u64 incl = carry + block_incl_scan(s, sh, tile & 1, &total);
+    u64 rank = incl - s;
+#pragma unroll
+    for (int j = 0; j < kSampVec; ++j) {
+      if (eq[j]) {
+        if (rank < need) {
+          const int slot = n_above + static_cast<int>(rank);  // < k
+          ls.idx[slot] = i0 + j;
+          ls.val[slot] = z[j];
+        }
+        ++rank;
+      }
+    }
+    carry += total;
+    if (carry >= need) break;  // uniform: every thread has the tile total
+    cur = nxt;
+  }
+  __syncthreads();
+
+  // ---- rank the k entries: key descending, then index ascending
+  if (tid < k) {
+    const int my_i = ls.idx[tid];
+    const float my_v = ls.val[tid];
+    const u32 my_key = float_key(my_v);
+    int pos = 0;
+    for (int j = 0; j < k; ++j) {
+      const u32 key = float_key(ls.val[j]);
+      pos += (key > my_key || (key == my_key && ls.idx[j] < my_i)) ? 1 : 0;
+    }
+    top_ids[static_cast<size_t>(r_i) * W + pos] = my_i;
+    top_lp[static_cast<size_t>(r_i) * W + pos] = lp_of(my_v);
+  }
+}
+
 }  // namespace
 
 void launch_sample_tokens(int64_t* out, const float* logits,
@@ -390,6 +564,17 @@ void launch_sample_tokens(int64_t* out, const float* logits,
   hipLaunchKernelGGL(sample_tokens_kernel, dim3(T), dim3(kSampThreads), 0,
                      stream, out, logits, temperature, top_k, top_p, min_p,
                      rng, V, vec ? 1 : 0);
+}
+
+void launch_token_logprobs(float* chosen, int* top_ids, float* top_lp,
+                           const float* logits, const int64_t* token_ids,
+                           const int* num_top, int T, int V, int W,
+                           hipStream_t stream) {
+  const bool vec =
+      V % kSampVec == 0 && reinterpret_cast<uintptr_t>(logits) % 16 == 0;
+  hipLaunchKernelGGL(token_logprobs_kernel, dim3(T), dim3(kSampThreads), 0,
+                     stream, chosen, top_ids, top_lp, logits, token_ids,
+                     num_top, V, W, vec ? 1 : 0);
 }
 
 }  // namespace fi

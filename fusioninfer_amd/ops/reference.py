@@ -566,3 +566,49 @@ def penalty_counts_add(counts, slot_ids, token_ids):
         0, flat, torch.ones_like(flat, dtype=counts.dtype)
     )
     return counts
+
+
+# ---------------------------------------------------------------- logprobs
+
+def token_logprobs(logits, token_ids, num_top, out):
+    """Reference of the token_logprobs kernel and its CPU implementation.
+
+    logits [T, V] fp32, token_ids [T] int64, num_top [T] int32, out =
+    (chosen [T] fp32, top_ids [T, W] int32, top_lp [T, W] fp32), written in
+    place and returned. Per row t with num_top[t] >= 0 (a negative value
+    skips the row: nothing of `out` is touched):
+
+        lp = fp32(x - (m + log(sum(exp(x - m)))))   in float64, m = max x
+        chosen[t] = lp[token_ids[t]]                NaN outside [0, V)
+        k = min(num_top[t], W, V)
+        top_ids[t, :k] = the k largest logits' indices, ordered by (logit
+            descending, index ascending), -0.0 equal to +0.0
+        top_lp[t, :k] = their lp;  columns >= k: id -1, value -inf
+
+    -inf logits are ordinary values with lp = -inf; a row without a finite
+    entry has lp = -inf everywhere (no NaN)."""
+    chosen, top_ids, top_lp = out
+    T, V = logits.shape
+    W = top_ids.shape[1]
+    toks = token_ids.tolist()
+    for t, want in enumerate(num_top.tolist()):
+        if want < 0:
+            continue
+        x = logits[t].double()
+        m = x.max()
+        if m == float("-inf"):
+            lp = torch.full((V,), float("-inf"))
+        else:
+            lp = (x - (m + torch.log(torch.exp(x - m).sum()))).float()
+        tok = toks[t]
+        chosen[t] = lp[tok] if 0 <= tok < V else float("nan")
+        k = min(want, W, V)
+        top_ids[t] = -1
+        top_lp[t] = float("-inf")
+        if k > 0:
+            # a stable descending sort keeps equal values in index order
+            idx = torch.sort(logits[t] + 0.0, descending=True,
+                             stable=True).indices[:k]
+            top_ids[t, :k] = idx.to(top_ids.dtype)
+            top_lp[t, :k] = lp[idx]
+    return chosen, top_ids, top_lp

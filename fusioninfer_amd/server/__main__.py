@@ -50,6 +50,9 @@ def parse_args(argv=None):
                         "sequences take the host path")
     p.add_argument("--no-device-penalties", action="store_true",
                    help="fused sampler: keep all penalties on the host path")
+    p.add_argument("--no-device-logprobs", action="store_true",
+                   help="fused sampler: compute logprobs on the host path "
+                        "(such requests then leave pipelined decode)")
     p.add_argument("--kv-cache-dtype", choices=["auto", "fp8"], default="auto")
     p.add_argument("--swap-space", type=float, default=0.0,
                    help="GiB of CPU swap for preempted sequences (0=recompute)")
@@ -160,6 +163,7 @@ def build_engine_config(args):
         sampler_backend=args.sampler_backend,
         penalty_slots=args.penalty_slots,
         device_penalties=not args.no_device_penalties,
+        device_logprobs=not args.no_device_logprobs,
     )
 
 

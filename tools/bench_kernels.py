@@ -2,7 +2,7 @@
 
 Usage: python tools/bench_kernels.py
            [prefill|decode|elementwise|lora|sampling|sampling_e2e|penalties|
-            penalties_e2e|all]
+            penalties_e2e|logprobs|logprobs_e2e|all]
 Prints per-shape timing + achieved TFLOP/s (attention) or GB/s (memory ops).
 """
 
@@ -447,6 +447,143 @@ def bench_penalties_e2e(runs=3):
         torch.cuda.empty_cache()
 
 
+def _host_logprobs(logits, tokens, k):
+    """The torch path of LLMEngine._sample_and_emit for rows that ask for
+    logprobs: one log_softmax over the slice, then per row a topk and the
+    blocking float() / int() reads."""
+    lp = torch.log_softmax(logits, dim=-1)
+    out = []
+    for j, tok in enumerate(tokens):
+        top = {}
+        if k > 0:
+            vals, idx = lp[j].topk(k)
+            top = {int(t): float(v) for t, v in zip(idx, vals)}
+        out.append((float(lp[j, tok]), top))
+    return out
+
+
+def bench_logprobs():
+    """ops.token_logprobs against the torch path of _sample_and_emit on the
+    same logits: V = 151936, every row asking. The kernel is timed with
+    device events (median of 3 alternating rounds x 20 calls after a
+    warm-up); the torch path ends in host reads, so it is timed on the host
+    clock around a synchronise (median of 3 rounds x 5 calls). "kernel +
+    readback" adds the one device-to-host copy and the decoding into the
+    engine's entry format. GB/s counts one read of the logits; the kernel
+    reads a row two to seven times (max, sum, three descent levels, the
+    list pass, part of the tie scan), from the L2 after the first.
+    fused_add_rms_norm at [2048, 4096] runs in the same process as the
+    bandwidth yardstick."""
+    from fusioninfer_amd.engine.sampler import DeviceLogprobs
+
+    V = 151936
+    H = 4096
+    x = torch.randn(2048, H, dtype=torch.bfloat16, device="cuda")
+    r = torch.randn_like(x)
+    w = torch.randn(H, dtype=torch.bfloat16, device="cuda")
+    norm = lambda: ops.fused_add_rms_norm(x, r, w, 1e-6)  # noqa: E731
+    for _ in range(5):
+        norm()
+    t_norm = _median(_event_times_us(norm, 60))
+    print("== logprobs: token_logprobs vs log_softmax + per-row topk "
+          "(V=151936) ==")
+    print(f"fused_add_rms_norm [2048, 4096]: {t_norm:.1f} us, "
+          f"{2048 * H * 2 * 4 / t_norm / 1e3:.0f} GB/s")
+    print("| T | k | torch path us | kernel us | kernel GB/s (one read) | "
+          "kernel + readback us | torch/kernel |")
+    print("|---|---|---|---|---|---|---|")
+    for T in (8, 64, 256):
+        logits = torch.randn(T, V, device="cuda") * 4
+        sampled = torch.randint(0, V, (T,), device="cuda")
+        tokens = sampled.tolist()
+        for k in (0, 5, 20):
+            W = max(k, 1)
+            num_top = torch.full((T,), k, dtype=torch.int32, device="cuda")
+            buf = torch.empty(T * (1 + 2 * W), dtype=torch.int32,
+                              device="cuda")
+            out = DeviceLogprobs.sections(buf, T, W)
+            lp = DeviceLogprobs(buf, [k] * T, W)
+            kernel = lambda: ops.token_logprobs(  # noqa: E731
+                logits, sampled, num_top, out=out)
+
+            def full():
+                kernel()
+                return lp.entries(buf.cpu())
+
+            host = lambda: _host_logprobs(logits, tokens, k)  # noqa: E731
+            for fn in (kernel, full, host):
+                fn()
+            torch.cuda.synchronize()
+            t_k, t_full, t_host = [], [], []
+            for _ in range(3):
+                t_k += _event_times_us(kernel, 20)
+                t_full.append(timeit(full, iters=5, warmup=1) * 1e6)
+                t_host.append(timeit(host, iters=5, warmup=1) * 1e6)
+            mk, mf, mh = _median(t_k), _median(t_full), _median(t_host)
+            print(f"| {T} | {k} | {mh:.0f} | {mk:.1f} | "
+                  f"{T * V * 4 / mk / 1e3:.0f} | {mf:.0f} | "
+                  f"{mh / mk:.0f}x |", flush=True)
+
+
+def bench_logprobs_e2e(runs=3):
+    """End-to-end: the 4-layer Qwen3-0.6B test engine, fused backend, 64
+    greedy sequences with logprobs=5, 64 tokens each, device_logprobs on
+    and off, and the same batch without logprobs as the floor. One untimed
+    generation per engine first, then `runs` timed ones: wall ms per engine
+    step and pipelined steps taken."""
+    from fusioninfer_amd.config import (CacheConfig, EngineConfig,
+                                        SchedulerConfig)
+    from fusioninfer_amd.engine.llm_engine import LLMEngine
+    from fusioninfer_amd.engine.sequence import SamplingParams
+    from fusioninfer_amd.models.registry import get_model_config
+
+    print("== engine decode, 64 sequences with logprobs=5 (4-layer "
+          "Qwen3-0.6B, fused backend) ==")
+    print("| device_logprobs | logprobs | run | steps | ms/step | "
+          "num_async_steps |")
+    print("|---|---|---|---|---|---|")
+    for on, want in ((True, 5), (False, 5), (True, None)):
+        mc = get_model_config("Qwen3-0.6B")
+        mc.num_layers = 4
+        cfg = EngineConfig(
+            model=mc,
+            cache=CacheConfig(num_gpu_blocks=2048),
+            scheduler=SchedulerConfig(
+                max_num_seqs=64, max_num_batched_tokens=4096,
+                max_model_len=512,
+            ),
+            seed=7,
+            sampler_backend="fused",
+            device_logprobs=on,
+        )
+        torch.manual_seed(0)
+        eng = LLMEngine(cfg, device="cuda:0")
+
+        def run():
+            for i in range(64):
+                eng.add_request(
+                    [(7 * i + j) % 1000 + 10 for j in range(32)],
+                    SamplingParams(max_tokens=64, logprobs=want),
+                )
+            steps0, async0 = eng.num_steps, eng.num_async_steps
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            while eng.has_unfinished():
+                eng.step()
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            return (dt, eng.num_steps - steps0,
+                    eng.num_async_steps - async0)
+
+        run()
+        for i in range(runs):
+            dt, steps, n_async = run()
+            print(f"| {on} | {want} | {i} | {steps} | "
+                  f"{dt / steps * 1e3:.2f} | {n_async} |", flush=True)
+        del eng
+        torch.cuda.empty_cache()
+
+
 class _OneTarget:
     """Minimal stand-in for LoRASlots: one layer, one target."""
 
@@ -474,3 +611,7 @@ if __name__ == "__main__":
         bench_penalties()
     if which in ("penalties_e2e", "all"):
         bench_penalties_e2e()
+    if which in ("logprobs", "all"):
+        bench_logprobs()
+    if which in ("logprobs_e2e", "all"):
+        bench_logprobs_e2e()

@@ -303,7 +303,11 @@ class ModelRunner:
         cu = payload["cu"]
         tile_rows = ops_mod.prefill_tile_rows(payload["new_lens"])
         tile_seq, tile_row0 = ops_mod.build_prefill_tiles(
-            payload["new_lens"], device=dev, rows=tile_rows
+            payload["new_lens"], device=dev, rows=tile_rows,
+            ctx_starts=[
+                t - n
+                for t, n in zip(payload["total_lens"], payload["new_lens"])
+            ],
         )
         meta = AttnMetadata(
             num_prefill_tokens=cu[-1],
@@ -618,7 +622,11 @@ class ModelRunner:
         nd = len(d["ids"])
         tile_rows = ops_mod.prefill_tile_rows(payload["new_lens"])
         tile_seq, tile_row0 = ops_mod.build_prefill_tiles(
-            payload["new_lens"], device=dev, rows=tile_rows
+            payload["new_lens"], device=dev, rows=tile_rows,
+            ctx_starts=[
+                t - n
+                for t, n in zip(payload["total_lens"], payload["new_lens"])
+            ],
         )
         max_blocks = max(len(b) for b in d["bt"])
         dbt_np = np.zeros((nd, max_blocks), dtype=np.int32)

@@ -328,19 +328,48 @@ def prefill_tile_rows(seq_lens) -> int:
     return PREFILL_TILE_ROWS
 
 
-def build_prefill_tiles(seq_lens, device=None, rows=None):
+# FI_PF_TILE_ORDER=0 restores the prefill schedule as it was before the
+# heaviest-first order: the ascending tile table and the (tile, head) grid
+# with the tile fastest. Both schedules give the same bits (a tile's
+# arithmetic does not depend on when it is dispatched); the switch exists
+# for before/after measurements from one build. Read once at import.
+PF_TILE_ORDER = _os.environ.get("FI_PF_TILE_ORDER", "1") != "0"
+
+PREFILL_KV_TILE = 64  # kv tokens per K-loop step of the prefill kernel
+
+
+def build_prefill_tiles(seq_lens, device=None, rows=None, ctx_starts=None,
+                        heaviest_first=None):
     """Host-side tile table for the prefill kernel: one workgroup per
     `rows` q-rows of each sequence (rows must be 128 or 256 and MATCH
     the tile_rows passed to the kernel).
 
-    seq_lens: list[int]. Returns (tile_seq, tile_row0) int32 tensors.
+    seq_lens: list[int], the NEW tokens per sequence; ctx_starts: list[int],
+    the tokens already cached per sequence (default: zeros).
+    Returns (tile_seq, tile_row0) int32 tensors.
+
+    Tiles are listed heaviest first: a causal tile walks
+    ceil((ctx_start + min(row0 + rows, L)) / 64) KV steps, and the kernel
+    hands tiles out in table order, so the long ones start first and the
+    short ones fill the tail (ties: ascending (seq, row0), so the table is
+    a pure function of its inputs). The kernel accepts any order;
+    heaviest_first=False keeps the ascending (seq, row0) one, and None
+    takes the process default (on unless FI_PF_TILE_ORDER=0).
     """
     rows = rows or PREFILL_TILE_ROWS
-    tile_seq, tile_row0 = [], []
-    for s, L in enumerate(seq_lens):
+    if heaviest_first is None:
+        heaviest_first = PF_TILE_ORDER
+    if ctx_starts is None:
+        ctx_starts = [0] * len(seq_lens)
+    tiles = []
+    for s, (L, c) in enumerate(zip(seq_lens, ctx_starts)):
         for r0 in range(0, L, rows):
-            tile_seq.append(s)
-            tile_row0.append(r0)
+            cost = -(-(c + min(r0 + rows, L)) // PREFILL_KV_TILE)
+            tiles.append((-cost, s, r0))
+    if heaviest_first:
+        tiles.sort()
+    tile_seq = [t[1] for t in tiles]
+    tile_row0 = [t[2] for t in tiles]
     return (
         torch.tensor(tile_seq, dtype=torch.int32, device=device),
         torch.tensor(tile_row0, dtype=torch.int32, device=device),
@@ -369,7 +398,8 @@ def prefill_attention(
             )
         out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
         _C.prefill_attention(out, q, k, v, tile_seq, tile_row0, cu_seqlens,
-                             scale, tile_rows or PREFILL_TILE_ROWS)
+                             scale, tile_rows or PREFILL_TILE_ROWS,
+                             PF_TILE_ORDER)
         return out
     return ref.prefill_attention(q, k, v, cu_seqlens, scale, causal=True)
 
@@ -397,16 +427,17 @@ def prefill_attention_paged(
         _require_native()
         if tile_seq is None:
             lens = (cu_seqlens_q[1:] - cu_seqlens_q[:-1]).tolist()
+            ctx = [k_len - n for k_len, n in zip(seq_lens_k.tolist(), lens)]
             tile_rows = tile_rows or prefill_tile_rows(lens)
             tile_seq, tile_row0 = build_prefill_tiles(
-                lens, device=q.device, rows=tile_rows
+                lens, device=q.device, rows=tile_rows, ctx_starts=ctx
             )
         if out is None:
             out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
         _C.prefill_attention_paged(
             out, q, k_cache, v_cache, tile_seq, tile_row0, cu_seqlens_q,
             block_tables, seq_lens_k, scale,
-            tile_rows or PREFILL_TILE_ROWS,
+            tile_rows or PREFILL_TILE_ROWS, PF_TILE_ORDER,
         )
         return out
     res = ref.prefill_attention_paged(

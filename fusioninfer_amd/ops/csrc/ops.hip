@@ -37,7 +37,7 @@ void launch_paged_attn_decode(u16*, float*, float*, const u16*, const void*,
 void launch_prefill_attn(u16*, const u16*, const void*, const void*,
                          const int*, const int*, const int*, const int*,
                          const int*, int, int, int64_t, int64_t, int64_t, int,
-                         int, int, float, bool, int, hipStream_t);
+                         int, int, float, bool, int, bool, hipStream_t);
 void launch_moe_gemm(u16*, const u16*, const u16*, const int*, const int*,
                      const int*, int, int, int, int, bool, hipStream_t);
 void launch_moe_gemm_fp8(u16*, const unsigned char*, const float*,
@@ -367,7 +367,7 @@ void paged_attention_decode(at::Tensor out, at::Tensor q, at::Tensor k_cache,
 void prefill_attention(at::Tensor out, at::Tensor q, at::Tensor k,
                        at::Tensor v, at::Tensor tile_seq, at::Tensor tile_row0,
                        at::Tensor cu_seqlens, double scale,
-                       int64_t tile_rows) {
+                       int64_t tile_rows, bool heads_adjacent) {
   TORCH_CHECK(tile_rows == 128 || tile_rows == 256,
               "tile_rows must be 128 or 256");
   CHECK_BF16_CUDA(out);
@@ -382,20 +382,23 @@ void prefill_attention(at::Tensor out, at::Tensor q, at::Tensor k,
   TORCH_CHECK(q.stride(2) == 1 && q.stride(1) == head_dim);
   TORCH_CHECK(k.stride(2) == 1 && k.stride(1) == head_dim);
   TORCH_CHECK(v.stride(2) == 1 && v.stride(1) == head_dim);
+  TORCH_CHECK(tile_seq.size(0) * q.size(1) < (int64_t{1} << 31),
+              "too many (tile, head) workgroups for one grid");
   fi::launch_prefill_attn(
       bf16_ptr(out), bf16_cptr(q), bf16_cptr(k), bf16_cptr(v),
       tile_seq.data_ptr<int>(), tile_row0.data_ptr<int>(),
       cu_seqlens.data_ptr<int>(), nullptr, nullptr, 0, tile_seq.size(0),
       q.stride(0), k.stride(0), v.stride(0), num_q_heads, num_kv_heads,
       head_dim, static_cast<float>(scale), false,
-      static_cast<int>(tile_rows / 32), current_stream());
+      static_cast<int>(tile_rows / 32), heads_adjacent, current_stream());
 }
 
 void prefill_attention_paged(at::Tensor out, at::Tensor q, at::Tensor k_cache,
                              at::Tensor v_cache, at::Tensor tile_seq,
                              at::Tensor tile_row0, at::Tensor cu_seqlens,
                              at::Tensor block_tables, at::Tensor seq_lens_k,
-                             double scale, int64_t tile_rows) {
+                             double scale, int64_t tile_rows,
+                             bool heads_adjacent) {
   TORCH_CHECK(tile_rows == 128 || tile_rows == 256,
               "tile_rows must be 128 or 256");
   CHECK_BF16_CUDA(out);
@@ -415,6 +418,8 @@ void prefill_attention_paged(at::Tensor out, at::Tensor q, at::Tensor k_cache,
   TORCH_CHECK(q.stride(2) == 1 && q.stride(1) == head_dim);
   TORCH_CHECK(out.is_contiguous() && out.sizes() == q.sizes(),
               "out must be a contiguous [T, Hq, D] tensor");
+  TORCH_CHECK(tile_seq.size(0) * q.size(1) < (int64_t{1} << 31),
+              "too many (tile, head) workgroups for one grid");
   fi::launch_prefill_attn(
       bf16_ptr(out), bf16_cptr(q), k_cache.data_ptr(), v_cache.data_ptr(),
       tile_seq.data_ptr<int>(), tile_row0.data_ptr<int>(),
@@ -422,7 +427,7 @@ void prefill_attention_paged(at::Tensor out, at::Tensor q, at::Tensor k_cache,
       seq_lens_k.data_ptr<int>(), block_tables.size(1), tile_seq.size(0),
       q.stride(0), 0, 0, num_q_heads, num_kv_heads, head_dim,
       static_cast<float>(scale), fp8,
-      static_cast<int>(tile_rows / 32), current_stream());
+      static_cast<int>(tile_rows / 32), heads_adjacent, current_stream());
 }
 
 // Shape checks shared by the bf16 and fp8 grouped GEMMs (dtype checks

@@ -88,7 +88,8 @@ __global__ __launch_bounds__(NW * kWaveSize, WPS) void prefill_attn_kernel(
     const int* __restrict__ seq_lens_k,    // [S] total ctx len (PAGED)
     const int max_blocks,
     const int64_t q_stride, const int64_t k_stride, const int64_t v_stride,
-    const int num_q_heads, const int num_kv_heads, const float scale) {
+    const int num_q_heads, const int num_kv_heads, const float scale,
+    const int heads_adjacent) {
   using CT = typename std::conditional<FP8, unsigned char, u16>::type;
   const CT* k = static_cast<const CT*>(k_p);
   const CT* v = static_cast<const CT*>(v_p);
@@ -104,7 +105,20 @@ __global__ __launch_bounds__(NW * kWaveSize, WPS) void prefill_attn_kernel(
   // reads.
   constexpr int kVTRowB = 128;
 
-  const int head = blockIdx.y;
+  // id -> (tile, head). heads_adjacent: 1-D grid, head fastest, so the q
+  // heads of one KV group are consecutive workgroups and the tile table
+  // is walked in its given order (the host lists the heaviest causal
+  // tiles first). Otherwise the 2-D (tile, head) grid, tile fastest.
+  // Uniform per launch; nothing below depends on which map was used.
+  // readfirstlane: the quotient of two uniform values comes out of the
+  // VALU; without it head and tile (and the table reads and address math
+  // that hang off them) stay in VGPRs — +2 VGPRs in three variants.
+  int head = blockIdx.y, tile = blockIdx.x;
+  if (heads_adjacent) {
+    const int id = blockIdx.x;
+    tile = __builtin_amdgcn_readfirstlane(id / num_q_heads);
+    head = id - tile * num_q_heads;
+  }
   const int kv_head = head / (num_q_heads / num_kv_heads);
   const int tid = threadIdx.x;
   const int wave = tid / kWaveSize;
@@ -112,12 +126,12 @@ __global__ __launch_bounds__(NW * kWaveSize, WPS) void prefill_attn_kernel(
   const int col = lane & 31;           // this lane's q row (within the wave)
   const int hi1 = lane >> 5;
 
-  const int seq = tile_seq[blockIdx.x];
+  const int seq = tile_seq[tile];
   const int seq_start = cu_seqlens[seq];
   const int seq_len = cu_seqlens[seq + 1] - seq_start;  // NEW q rows
   const int k_len = PAGED ? seq_lens_k[seq] : seq_len;  // total kv rows
   const int ctx_start = k_len - seq_len;
-  const int wg_row0 = tile_row0[blockIdx.x];
+  const int wg_row0 = tile_row0[tile];
   const int row0 = wg_row0 + wave * kQPerWave;
   const bool active = row0 < seq_len;
   const int* bt_row = PAGED
@@ -516,12 +530,19 @@ void launch_prefill_attn(u16* out, const u16* q, const void* k, const void* v,
                          const int* seq_lens_k, int max_blocks, int ntiles,
                          int64_t q_stride, int64_t k_stride, int64_t v_stride,
                          int num_q_heads, int num_kv_heads, int head_dim,
-                         float scale, bool fp8, int nw, hipStream_t stream) {
+                         float scale, bool fp8, int nw, bool heads_adjacent,
+                         hipStream_t stream) {
   const bool paged = block_tables != nullptr;
   // nw = waves per workgroup (4 or 8), chosen per batch by the host
   // (ops.prefill_tile_rows: 128-row tiles for long sequences); the tile
   // table must have been built with rows == nw*32
-  dim3 grid(ntiles, num_q_heads), block(nw * kWaveSize);
+  // heads_adjacent: one workgroup per (tile, head) on a 1-D grid with the
+  // head fastest; else the 2-D grid with the tile fastest (see the kernel)
+  const dim3 grid = heads_adjacent
+      ? dim3(static_cast<unsigned>(ntiles) * num_q_heads)
+      : dim3(ntiles, num_q_heads);
+  const dim3 block(nw * kWaveSize);
+  const int adj = heads_adjacent ? 1 : 0;
 #define FI_PF_LAUNCH(DD, PP, F8)                                              \
   do {                                                                        \
     if (nw == 4)                                                              \
@@ -529,13 +550,13 @@ void launch_prefill_attn(u16* out, const u16* q, const void* k, const void* v,
                          block, 0, stream, out, q, k, v, tile_seq,            \
                          tile_row0, cu_seqlens, block_tables, seq_lens_k,     \
                          max_blocks, q_stride, k_stride, v_stride,            \
-                         num_q_heads, num_kv_heads, scale);                   \
+                         num_q_heads, num_kv_heads, scale, adj);              \
     else                                                                      \
       hipLaunchKernelGGL((prefill_attn_kernel<DD, PP, F8, 2, 8>), grid,       \
                          block, 0, stream, out, q, k, v, tile_seq,            \
                          tile_row0, cu_seqlens, block_tables, seq_lens_k,     \
                          max_blocks, q_stride, k_stride, v_stride,            \
-                         num_q_heads, num_kv_heads, scale);                   \
+                         num_q_heads, num_kv_heads, scale, adj);              \
   } while (0)
   if (fp8 && !paged) abort();  // fp8 KV is a cache format; dense is bf16
   if (head_dim == 128) {

@@ -30,21 +30,82 @@ def timeit(fn, iters=20, warmup=5):
 
 
 def bench_prefill():
+    """Dense and paged prefill at the Qwen3-8B head counts, both schedules
+    from one process: `off` is the ascending tile table on the (tile, head)
+    grid (what FI_PF_TILE_ORDER=0 selects), `on` the heaviest-first table
+    with the heads of a tile adjacent. The module flag is flipped between
+    calls; tables are prebuilt, tile_rows as the engine picks them
+    (ops.prefill_tile_rows). Device-event time per call, median of 3
+    alternating rounds x 20 calls after a warm-up of each. The paged rows
+    read a bf16 cache with shuffled block ids and no cached prefix, the
+    benchmark's prefill step."""
     print("== prefill attention (varlen causal, GQA 32/8, D=128) ==")
-    for nseq, L in [(1, 1024), (8, 1024), (4, 2048), (1, 8192), (16, 512)]:
-        Hq, Hk, D = 32, 8, 128
+    print("| kind | shape | tile_rows | off us | off TF/s | on us | on TF/s "
+          "| off/on |")
+    print("|---|---|---|---|---|---|---|---|")
+    Hq, Hk, D, bs = 32, 8, 128, 16
+    scale = 1.0 / math.sqrt(D)
+    shapes = [("dense", 1, 1024), ("dense", 8, 1024), ("dense", 4, 2048),
+              ("dense", 1, 8192), ("dense", 16, 512), ("paged", 8, 1024),
+              ("paged", 1, 8192)]
+    for kind, nseq, L in shapes:
         T = nseq * L
         q = torch.randn(T, Hq, D, dtype=torch.bfloat16, device="cuda")
-        k = torch.randn(T, Hk, D, dtype=torch.bfloat16, device="cuda")
-        v = torch.randn(T, Hk, D, dtype=torch.bfloat16, device="cuda")
         cu = torch.arange(0, nseq + 1, dtype=torch.int32, device="cuda") * L
         lens = [L] * nseq
-        ts, tr = ops.build_prefill_tiles(lens, device="cuda")
-        scale = 1.0 / math.sqrt(D)
-        t = timeit(lambda: ops.prefill_attention(q, k, v, cu, scale, ts, tr))
+        rows = ops.prefill_tile_rows(lens)
+        tables = {
+            on: ops.build_prefill_tiles(lens, device="cuda", rows=rows,
+                                        heaviest_first=on)
+            for on in (False, True)
+        }
+        if kind == "dense":
+            k = torch.randn(T, Hk, D, dtype=torch.bfloat16, device="cuda")
+            v = torch.randn_like(k)
+
+            def call(on):
+                ts, tr = tables[on]
+                return ops.prefill_attention(q, k, v, cu, scale, ts, tr, rows)
+        else:
+            nblk = L // bs
+            kc = torch.randn(nseq * nblk + 1, Hk, bs, D,
+                             dtype=torch.bfloat16, device="cuda")
+            vc = torch.randn_like(kc)
+            bt = (1 + torch.randperm(nseq * nblk, device="cuda")).int()
+            bt = bt.view(nseq, nblk).contiguous()
+            slk = torch.full((nseq,), L, dtype=torch.int32, device="cuda")
+            out = torch.empty_like(q)
+
+            def call(on):
+                ts, tr = tables[on]
+                return ops.prefill_attention_paged(
+                    q, kc, vc, bt, cu, slk, scale, ts, tr, rows, out=out)
+
+        def run(on):
+            ops.PF_TILE_ORDER = on  # selects the dispatch map per call
+            return call(on)
+
+        default = ops.PF_TILE_ORDER
+        try:
+            first = run(False).clone()  # the paged calls share `out`
+            same = torch.equal(first, run(True))
+            times = {False: [], True: []}
+            for on in times:
+                for _ in range(5):
+                    run(on)
+            torch.cuda.synchronize()
+            for _ in range(3):
+                for on in times:
+                    times[on] += _event_times_us(lambda: run(on), 20)
+        finally:
+            ops.PF_TILE_ORDER = default
+        assert same, "the two schedules must give the same bits"
         # causal flops: 2 matmuls * L*(L+1)/2 * D * 2 per head
         flops = nseq * Hq * 2 * (L * (L + 1) / 2) * D * 2
-        print(f"  {nseq}x{L}: {t*1e6:8.1f} us  {flops/t/1e12:7.1f} TF/s")
+        off, on = _median(times[False]), _median(times[True])
+        print(f"| {kind} | {nseq}x{L} | {rows} | {off:.1f} | "
+              f"{flops / off / 1e6:.0f} | {on:.1f} | {flops / on / 1e6:.0f} "
+              f"| {off / on:.2f}x |", flush=True)
 
 
 def bench_decode(group=4):

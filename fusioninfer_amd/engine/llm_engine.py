@@ -14,10 +14,13 @@ from typing import Dict, List, Optional
 
 import torch
 
+from fusioninfer_amd import ops
 from fusioninfer_amd.config import EngineConfig
 from fusioninfer_amd.engine.block_manager import BlockManager
 from fusioninfer_amd.engine.model_runner import ModelRunner
-from fusioninfer_amd.engine.sampler import Sampler, device_logprobs_top
+from fusioninfer_amd.engine.sampler import (
+    Sampler, _has_penalties, device_logprobs_top,
+)
 from fusioninfer_amd.engine.scheduler import Scheduler
 from fusioninfer_amd.engine.sequence import SamplingParams, Sequence, SeqStatus
 
@@ -100,6 +103,15 @@ class LLMEngine:
                 "ngram method under TP/PP"
             )
         self.proposer = build_proposer(cfg.speculative, cfg, device)
+        # fused backend: drafted spans are verified by the sampler on the
+        # device (Sampler.verify_drafts), which also serves sampled,
+        # penalised and logprobs requests; sampled_verify=False keeps the
+        # greedy-only eligibility
+        self._device_verify = (self.proposer is not None
+                               and cfg.sampler_backend == "fused")
+        if self._device_verify and getattr(
+                cfg.speculative, "sampled_verify", True):
+            self.proposer.draftable = self._seq_draftable
         self.num_spec_draft_tokens = 0
         self.num_spec_accepted_tokens = 0
         self.runner.capture_decode_graphs()
@@ -958,6 +970,9 @@ class LLMEngine:
         drafts = [list(d) for d in self.proposer.propose_all(decode_seqs)]
         any_d = False
         for s, d in zip(decode_seqs, drafts):
+            if self._device_verify:
+                # kernel contract of the verify pass
+                del d[ops.SPEC_MAX_DRAFT:]
             if d:
                 last_pos = s.num_tokens - 1 + len(d)
                 if bm.extra_blocks_for(s, last_pos) > bm.num_free():
@@ -967,12 +982,33 @@ class LLMEngine:
             any_d = any_d or bool(d)
         return drafts if any_d else None
 
+    def _seq_draftable(self, s: Sequence) -> bool:
+        """Draft eligibility when Sampler.verify_drafts does the
+        verification (fused backend): any temperature; penalties when the
+        sequence holds a slot of the device penalty table or one is free;
+        logprobs when ops.token_logprobs serves them. Grammar masks,
+        logit_bias and prompt_logprobs stay outside."""
+        sp = s.sampling
+        return (
+            sp.guided is None
+            and not sp.logit_bias
+            and sp.prompt_logprobs is None
+            and (sp.logprobs is None
+                 or (self.sampler.device_logprobs
+                     and device_logprobs_top(sp) >= 0))
+            and (not _has_penalties(sp)
+                 or self.sampler.penalty_slot_available(s))
+        )
+
     def _finish_spec_step(self, batch, payload, logits, drafts):
-        """Greedy draft acceptance. Logits row layout (see
-        build_spec_payload): [completing-prefill rows | per decode seq,
-        1 + k_i rows]. Draft-less decode seqs go through the regular
-        sampler; drafted seqs accept the longest matching prefix plus the
-        corrected token — token-exact with non-speculative greedy."""
+        """Draft acceptance. Logits row layout (see build_spec_payload):
+        [completing-prefill rows | per decode seq, 1 + k_i rows].
+        Draft-less decode seqs go through the regular sampler; drafted seqs
+        accept the longest matching prefix plus the corrected token. With
+        the torch backend that is a host argmax comparison (greedy
+        requests only), token-exact with non-speculative greedy; with the
+        fused backend Sampler.verify_drafts samples, compares and counts on
+        the device for every drafted span."""
         logits_f = logits.float()
         n_prefill = len(batch.prefill_seqs)
         pf_flags = payload["sample"][:n_prefill]
@@ -992,7 +1028,29 @@ class LLMEngine:
             outputs.extend(
                 self._sample_and_emit(samp_seqs, logits_f[samp_rows])
             )
-        if spec:
+        if spec and self._device_verify:
+            rows = [r0 + j for _, d, r0 in spec for j in range(len(d) + 1)]
+            sub = logits_f
+            if len(rows) != logits_f.shape[0]:
+                sub = logits_f[rows]
+            emitted, accepted, lps = self.sampler.verify_drafts(
+                sub, [(s, d) for s, d, _ in spec]
+            )
+            for i, (s, d, _) in enumerate(spec):
+                self.num_spec_draft_tokens += len(d)
+                self.num_spec_accepted_tokens += accepted[i]
+                if lps is not None and lps[i] is not None:
+                    s.logprobs.extend(lps[i])
+                out = self._emit_tokens(s, emitted[i])
+                cut = len(emitted[i]) - len(out.new_token_ids)
+                if cut and lps is not None and lps[i] is not None:
+                    # stopped inside the span: one entry per emitted token
+                    del s.logprobs[-cut:]
+                    out.logprobs = list(s.logprobs)
+                outputs.append(out)
+                if not s.is_finished():
+                    self.proposer.commit(s, accepted[i])
+        elif spec:
             greedy = logits_f.argmax(dim=-1).tolist()
             for s, d, r0 in spec:
                 k = len(d)

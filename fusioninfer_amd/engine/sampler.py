@@ -4,6 +4,7 @@ exposes."""
 
 from __future__ import annotations
 
+import copy
 from typing import List
 
 import torch
@@ -388,6 +389,67 @@ class Sampler:
             sampled[rows] = draw
         return sampled
 
+    def _pack_rows(self, rows, slots=None, num_top=None, tail_words=0):
+        """The host side of one fused sampling pass: per-row parameters in
+        ONE int32 buffer, so that a single copy takes them to the device.
+        rows: (sequence, j) per logits row, j = tokens the row is ahead of
+        the sequence's output (0 for a plain step, the row's index inside
+        its span under speculative verification). Layout, T = len(rows):
+
+            [0, 8T)    temperature | top_k | top_p | min_p | rng (T x 2
+                       int64: (seed, len(output) + j) for seeded rows,
+                       (engine seed, 2^62 + running counter) for unseeded
+                       ones, (0, 0) at temperature 0)
+            [8T, 13T)  only when a slot of `slots` is live: (rp, 1/rp,
+                       presence, frequency) as [T, 4] fp32, then the slots
+            + T        only with num_top: one int per row
+            + tail     tail_words more words for the caller, starting at an
+                       even word (int64 views are possible there)
+
+        Returns (buffer, live, pen_words, tail); pen_words is 13 or 8, tail
+        the first word of the caller's part."""
+        T = len(rows)
+        live = slots is not None and any(slot >= 0 for slot in slots)
+        pen_words = 13 if live else 8
+        words = (pen_words + (1 if num_top is not None else 0)) * T
+        tail = words + (words & 1)
+        temps, ks, ps, mps, rng = [], [], [], [], []
+        for s, j in rows:
+            sp = s.sampling
+            temps.append(sp.temperature)
+            ks.append(min(max(int(sp.top_k), 0), 2**31 - 1))
+            ps.append(sp.top_p)
+            mps.append(sp.min_p)
+            if sp.temperature == 0:
+                rng.append((0, 0))
+            elif sp.seed is not None:
+                rng.append((_as_i64(sp.seed), len(s.output_token_ids) + j))
+            else:
+                rng.append((
+                    _as_i64(self.base_seed),
+                    _as_i64(_UNSEEDED_OFFSET_BASE + self.num_unseeded_draws),
+                ))
+                self.num_unseeded_draws += 1
+        host = torch.empty(tail + tail_words if tail_words else words,
+                           dtype=torch.int32)
+        host[:T].view(torch.float32).copy_(torch.tensor(temps))
+        host[T:2 * T].copy_(torch.tensor(ks, dtype=torch.int32))
+        host[2 * T:3 * T].view(torch.float32).copy_(torch.tensor(ps))
+        host[3 * T:4 * T].view(torch.float32).copy_(torch.tensor(mps))
+        host[4 * T:8 * T].view(torch.int64).copy_(
+            torch.tensor(rng, dtype=torch.int64).flatten()
+        )
+        if live:
+            host[8 * T:12 * T].view(torch.float32).copy_(torch.tensor(
+                [penalty_params(s.sampling) for s, _ in rows],
+                dtype=torch.float32,
+            ).flatten())
+            host[12 * T:13 * T].copy_(torch.tensor(slots, dtype=torch.int32))
+        if num_top is not None:
+            host[pen_words * T:words].copy_(
+                torch.tensor(num_top, dtype=torch.int32))
+        return host, live, pen_words, tail
+
     def _sample_fused(self, logits: torch.Tensor, seqs: List[Sequence],
                       slots=None, num_top=None):
         """One ops.sample_tokens call for the whole mixed batch. The per-row
@@ -411,43 +473,8 @@ class Sampler:
         from fusioninfer_amd import ops
 
         T = len(seqs)
-        live = slots is not None and any(slot >= 0 for slot in slots)
-        pen_words = 13 if live else 8
-        words = pen_words + (1 if num_top is not None else 0)
-        temps, ks, ps, mps, rng = [], [], [], [], []
-        for s in seqs:
-            sp = s.sampling
-            temps.append(sp.temperature)
-            ks.append(min(max(int(sp.top_k), 0), 2**31 - 1))
-            ps.append(sp.top_p)
-            mps.append(sp.min_p)
-            if sp.temperature == 0:
-                rng.append((0, 0))
-            elif sp.seed is not None:
-                rng.append((_as_i64(sp.seed), len(s.output_token_ids)))
-            else:
-                rng.append((
-                    _as_i64(self.base_seed),
-                    _as_i64(_UNSEEDED_OFFSET_BASE + self.num_unseeded_draws),
-                ))
-                self.num_unseeded_draws += 1
-        host = torch.empty(words * T, dtype=torch.int32)
-        host[:T].view(torch.float32).copy_(torch.tensor(temps))
-        host[T:2 * T].copy_(torch.tensor(ks, dtype=torch.int32))
-        host[2 * T:3 * T].view(torch.float32).copy_(torch.tensor(ps))
-        host[3 * T:4 * T].view(torch.float32).copy_(torch.tensor(mps))
-        host[4 * T:8 * T].view(torch.int64).copy_(
-            torch.tensor(rng, dtype=torch.int64).flatten()
-        )
-        if live:
-            host[8 * T:12 * T].view(torch.float32).copy_(torch.tensor(
-                [penalty_params(s.sampling) for s in seqs],
-                dtype=torch.float32,
-            ).flatten())
-            host[12 * T:13 * T].copy_(torch.tensor(slots, dtype=torch.int32))
-        if num_top is not None:
-            host[pen_words * T:].copy_(
-                torch.tensor(num_top, dtype=torch.int32))
+        host, live, pen_words, _ = self._pack_rows(
+            [(s, 0) for s in seqs], slots, num_top)
         dev = host.to(logits.device)
         if logits.dtype != torch.float32:
             logits = logits.float()
@@ -486,3 +513,163 @@ class Sampler:
             out=DeviceLogprobs.sections(buf, T, W),
         )
         return sampled, DeviceLogprobs(buf, num_top, W)
+
+    def verify_drafts(self, logits: torch.Tensor, spans):
+        """Speculative verification for every drafted span of a step, in
+        one pass (fused backend only).
+
+        spans: (sequence, draft tokens) in row order; a span with k drafts
+        owns 1 + k rows of logits [R, V]: row j holds the target's logits
+        after the history plus drafts[:j]. Both proposers draft
+        deterministically, so the draft distribution is one-hot and
+        rejection sampling is exact in this form: every row is sampled from
+        the target distribution with the span's parameters (row j of a
+        seeded request at (seed, len(output) + j), the pair the plain fused
+        step would use there), draft j is accepted iff row j's sample equals
+        it (probability p(draft)), and the first mismatching sample is the
+        corrected token (p restricted to != draft, the residual
+        distribution). Greedy spans are the temperature-0 case of the same
+        kernel.
+
+        Row j's penalties count the history plus drafts[:j]
+        (ops.apply_penalties_spec on the span's PenaltyTable row); after
+        ops.spec_accept the emitted tokens are added to the table device
+        to device and counted_len advances by the number emitted. If the
+        engine then stops inside the span (stop token), counted_len and the
+        history disagree, and the slot is released or rebuilt at its next
+        sync. Penalised spans without a slot take the host
+        _apply_penalties row by row. Logprobs come from one
+        ops.token_logprobs launch over all rows, after penalties and before
+        temperature.
+
+        One host-to-device copy (parameters, drafts, span bounds), at most
+        two back (emitted tokens + counts; the logprobs buffer). Returns
+        (emitted: list of token lists, accepted: list of int, logprobs:
+        list with, per span, the entries of its emitted rows or None — or
+        None when no span asked)."""
+        from fusioninfer_amd import ops
+
+        if self.backend != "fused":
+            raise RuntimeError("verify_drafts needs the fused sampler backend")
+        S = len(spans)
+        V = logits.shape[-1]
+        rows, cu = [], [0]
+        for seq, draft in spans:
+            if len(draft) > ops.SPEC_MAX_DRAFT:
+                raise ValueError(
+                    f"verify_drafts: a draft of {len(draft)} tokens exceeds "
+                    f"SPEC_MAX_DRAFT = {ops.SPEC_MAX_DRAFT}")
+            rows.extend((seq, j) for j in range(len(draft) + 1))
+            cu.append(len(rows))
+        R = len(rows)
+        if S < 1 or tuple(logits.shape) != (R, V):
+            raise ValueError(
+                f"verify_drafts: {S} spans with {R} rows, logits "
+                f"{tuple(logits.shape)}")
+        W = max(len(d) for _, d in spans) + 1
+        E = max(W - 1, 1)
+        span_seqs = [seq for seq, _ in spans]
+        penalised = [_has_penalties(s.sampling) for s in span_seqs]
+        span_slots = [-1] * S
+        if self.penalty_table is not None and any(penalised):
+            span_slots = self.penalty_table.sync(span_seqs, V)
+        slots = [span_slots[i] for i in range(S) for _ in range(cu[i], cu[i + 1])]
+        num_top = None
+        if self.device_logprobs:
+            span_top = [device_logprobs_top(s.sampling) for s in span_seqs]
+            if any(k >= 0 for k in span_top):
+                num_top = [span_top[i] for i in range(S)
+                           for _ in range(cu[i], cu[i + 1])]
+
+        live = any(slot >= 0 for slot in span_slots)
+        # the caller's part of the buffer: drafts [R] int64 | extra [R, E]
+        # int64 (live only) | span_cu [S + 1] | span slots [S] (live only)
+        n_extra = 2 * R * E if live else 0
+        tail_words = 2 * R + n_extra + (S + 1) + (S if live else 0)
+        host, _, pen_words, tail = self._pack_rows(
+            rows, slots, num_top, tail_words)
+        drafts_h = host[tail:tail + 2 * R].view(torch.int64)
+        drafts_h.fill_(-1)
+        for i, (_, d) in enumerate(spans):
+            if d:
+                drafts_h[cu[i]:cu[i] + len(d)] = torch.tensor(
+                    d, dtype=torch.int64)
+        p = tail + 2 * R
+        if live:
+            extra_h = host[p:p + n_extra].view(torch.int64).view(R, E)
+            extra_h.fill_(-1)
+            for i, (_, d) in enumerate(spans):
+                for j in range(1, len(d) + 1):
+                    extra_h[cu[i] + j, :j] = drafts_h[cu[i]:cu[i] + j]
+            p += n_extra
+        host[p:p + S + 1].copy_(torch.tensor(cu, dtype=torch.int32))
+        if live:
+            host[p + S + 1:].copy_(torch.tensor(span_slots, dtype=torch.int32))
+        dev = host.to(logits.device)
+
+        if logits.dtype != torch.float32:
+            logits = logits.float()
+        logits = logits.contiguous()
+        for i, (seq, d) in enumerate(spans):
+            if penalised[i] and span_slots[i] < 0:
+                # no slot: the host ops, on the history as row j sees it
+                for j in range(len(d) + 1):
+                    ahead = copy.copy(seq)
+                    ahead.output_token_ids = seq.output_token_ids + d[:j]
+                    r = cu[i] + j
+                    self._apply_penalties(logits[r:r + 1], [ahead])
+        drafts_d = dev[tail:tail + 2 * R].view(torch.int64)
+        q = tail + 2 * R
+        if live:
+            counts = self.penalty_table.counts
+            ops.apply_penalties_spec(
+                logits, counts, dev[12 * R:13 * R],
+                dev[8 * R:12 * R].view(torch.float32).view(R, 4),
+                dev[q:q + n_extra].view(torch.int64).view(R, E),
+            )
+            q += n_extra
+        sampled = ops.sample_tokens(
+            logits,
+            dev[:R].view(torch.float32),
+            dev[R:2 * R],
+            dev[2 * R:3 * R].view(torch.float32),
+            dev[3 * R:4 * R].view(torch.float32),
+            dev[4 * R:8 * R].view(torch.int64).view(R, 2),
+        )
+        acc = torch.empty(ops.spec_accept_words(S, W), dtype=torch.int64,
+                          device=logits.device)
+        emitted_d, _ = ops.spec_accept(
+            sampled, drafts_d, dev[q:q + S + 1], W, out=acc)
+        if live:
+            # -1 columns (rejected tail) and -1 slots are skipped there
+            ops.penalty_counts_add(
+                counts,
+                dev[q + S + 1:].view(S, 1).expand(S, W).reshape(-1),
+                emitted_d.reshape(-1),
+            )
+        lp = None
+        if num_top is not None:
+            LW = max(max(num_top), 1)
+            buf = torch.empty(R * (1 + 2 * LW), dtype=torch.int32,
+                              device=logits.device)
+            ops.token_logprobs(
+                logits, sampled, dev[pen_words * R:(pen_words + 1) * R],
+                out=DeviceLogprobs.sections(buf, R, LW),
+            )
+            lp = DeviceLogprobs(buf, num_top, LW)
+
+        em_h, n_h = ops.spec_accept_sections(acc.cpu(), S, W)
+        em_h, n_h = em_h.tolist(), n_h.tolist()
+        emitted = [em_h[i][:n_h[i]] for i in range(S)]
+        accepted = [max(n - 1, 0) for n in n_h]
+        for slot, n in zip(span_slots, n_h):
+            if slot >= 0:
+                self.penalty_table._counted_len[slot] += n
+        if lp is None:
+            return emitted, accepted, None
+        entries = lp.entries(lp.buf.cpu())
+        logprobs = [
+            entries[cu[i]:cu[i] + n_h[i]] if span_top[i] >= 0 else None
+            for i in range(S)
+        ]
+        return emitted, accepted, logprobs

@@ -11,12 +11,22 @@ so the feature needs no extra model, no extra KV cache, and works
 unchanged under TP and PP (the verify payload is a plain "prefill"
 payload the driver already broadcasts).
 
-Acceptance is greedy (drafting is only enabled for temperature==0
-requests without penalties/logprobs/guided grammars): draft token j is
-accepted while it equals the argmax of the verification logits at row
-j-1; the first mismatch row contributes the corrected token, so every
-spec step emits between 1 and k+1 tokens and the output is TOKEN-EXACT
-with non-speculative greedy decoding.
+Acceptance with the torch sampler backend is greedy (drafting is only
+enabled for temperature==0 requests without penalties/logprobs/guided
+grammars): draft token j is accepted while it equals the argmax of the
+verification logits at row j-1; the first mismatch row contributes the
+corrected token, so every spec step emits between 1 and k+1 tokens and
+the output is TOKEN-EXACT with non-speculative greedy decoding.
+
+With the fused sampler backend the engine verifies on the device
+(Sampler.verify_drafts) and, with SpeculativeConfig.sampled_verify, hands
+the proposers a wider eligibility predicate (`draftable`): sampled,
+penalised and logprobs requests draft too. Both proposers draft
+deterministically, so the draft distribution is one-hot and rejection
+sampling is exact as "sample row j from the target distribution, accept
+draft j iff the sample equals it, emit the first mismatching sample";
+seeded requests draw row j at (seed, len(output) + j) and so emit what the
+non-speculative fused sampler emits from the same logits.
 
 KV bookkeeping: verification writes draft KV into the sequence's own
 slots (slot = block[pos//bs]*bs + pos%bs is deterministic per position),
@@ -56,6 +66,11 @@ class SpeculativeConfig:
     # req/s at concurrency 256 with accept_rate 0.22). Speculation is a
     # LATENCY feature for small batches. 0 disables the guard.
     disable_by_batch_size: int = 32
+    # fused sampler backend only: verify drafts by sampling on the device,
+    # which makes sampled (temperature > 0), penalised and logprobs
+    # requests draftable. False keeps drafting to what seq_is_draftable
+    # admits. No effect with the torch backend.
+    sampled_verify: bool = True
 
 
 def seq_is_draftable(seq: Sequence) -> bool:
@@ -109,9 +124,12 @@ def _seq_budget(seq: Sequence, k: int) -> int:
 class NgramProposer:
     def __init__(self, cfg: SpeculativeConfig):
         self.cfg = cfg
+        # eligibility predicate; the engine replaces it when its sampler
+        # can verify more than greedy requests
+        self.draftable = seq_is_draftable
 
     def propose(self, seq: Sequence) -> List[int]:
-        if not seq_is_draftable(seq):
+        if not self.draftable(seq):
             return []
         k = _seq_budget(seq, self.cfg.num_speculative_tokens)
         if k <= 0:
@@ -161,6 +179,7 @@ class DraftModelProposer:
         from fusioninfer_amd.models.registry import get_model_config
 
         self.cfg = cfg
+        self.draftable = seq_is_draftable  # see NgramProposer
         mc = get_model_config(cfg.model)
         assert mc.vocab_size == target_cfg.model.vocab_size, (
             "draft model must share the target's vocabulary"
@@ -216,7 +235,7 @@ class DraftModelProposer:
         live = []   # (idx, seq, st, budget)
         drafts: List[List[int]] = [[] for _ in seqs]
         for i, s in enumerate(seqs):
-            if not seq_is_draftable(s):
+            if not self.draftable(s):
                 continue
             budget = _seq_budget(s, k)
             if budget <= 0:

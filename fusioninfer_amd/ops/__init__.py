@@ -844,4 +844,163 @@ def penalty_counts_add(counts, slot_ids, token_ids):
     return ref.penalty_counts_add(counts, slot_ids, token_ids)
 
 
+# ------------------------------------------------- speculative verification
+
+SPEC_MAX_DRAFT = 16  # kernel contract: draft ids per row live in LDS
+
+
+def apply_penalties_spec(logits, counts, slot_ids, params, extra):
+    """apply_penalties for the rows of speculative verification spans, in
+    place on logits: row r also counts the draft tokens that precede it
+    inside its span.
+
+    logits [R, V] fp32 contiguous, counts [S, V] int32, slot_ids [R] int32,
+    params [R, 4] fp32 as in apply_penalties, extra [R, E] int64 with
+    1 <= E <= SPEC_MAX_DRAFT, padded with -1. The effective count of
+    column v in row r is
+
+        c = counts[slot_ids[r], v] + #{e : extra[r, e] == v}
+
+    and an element with c > 0 is penalised exactly as in apply_penalties
+    (same operations, same order, each rounded to fp32). Elements with
+    c == 0 and rows whose slot is outside [0, S) are left bit-for-bit
+    untouched; extra ids outside [0, V) (-1, V, 1 << 40) are ignored and
+    never used as an index. counts is only read. One launch, static grid,
+    no workspace, no host sync. Shape or dtype mismatch raises ValueError.
+    On the CPU this is reference.apply_penalties_spec."""
+    op = "apply_penalties_spec"
+    if logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1:
+        raise ValueError(
+            f"{op}: logits must be [R >= 1, V >= 1], got "
+            f"{tuple(logits.shape)}"
+        )
+    T, V = logits.shape
+    if logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise ValueError(
+            f"{op}: logits must be contiguous fp32 (the op works in place), "
+            f"got {logits.dtype} strides {logits.stride()}"
+        )
+    if T > PENALTY_MAX_ROWS or V >= 1 << 30:
+        raise ValueError(
+            f"{op}: need R <= {PENALTY_MAX_ROWS} and V < 2^30, got R={T} "
+            f"V={V}"
+        )
+    _check_penalty_counts(op, counts)
+    if counts.shape[1] != V:
+        raise ValueError(
+            f"{op}: counts has {counts.shape[1]} columns, logits {V}"
+        )
+    if (extra.dim() != 2 or extra.dtype != torch.int64
+            or extra.shape[0] != T
+            or not 1 <= extra.shape[1] <= SPEC_MAX_DRAFT):
+        raise ValueError(
+            f"{op}: extra must be int64 [{T}, 1 <= E <= {SPEC_MAX_DRAFT}], "
+            f"got {extra.dtype} {tuple(extra.shape)}"
+        )
+    for name, t, dtype, shape in (
+        ("slot_ids", slot_ids, torch.int32, (T,)),
+        ("params", params, torch.float32, (T, 4)),
+    ):
+        if t.dtype != dtype or tuple(t.shape) != shape:
+            raise ValueError(
+                f"{op}: {name} must be {dtype} {shape}, got {t.dtype} "
+                f"{tuple(t.shape)}"
+            )
+    for name, t in (("counts", counts), ("slot_ids", slot_ids),
+                    ("params", params), ("extra", extra)):
+        if t.device != logits.device:
+            raise ValueError(f"{op}: {name} is on {t.device}, logits on "
+                             f"{logits.device}")
+    if logits.is_cuda:
+        _require_native()
+        _C.apply_penalties_spec(logits, counts, slot_ids.contiguous(),
+                                params.contiguous(), extra.contiguous())
+        return logits
+    return ref.apply_penalties_spec(logits, counts, slot_ids, params, extra)
+
+
+def spec_accept_sections(buf: torch.Tensor, S: int, W: int):
+    """(emitted [S, W] int64, n_emit [S] int32) as views of one int64
+    buffer of spec_accept_words(S, W) elements."""
+    return (
+        buf[:S * W].view(S, W),
+        buf[S * W:].view(torch.int32)[:S],
+    )
+
+
+def spec_accept_words(S: int, W: int) -> int:
+    return S * W + (S + 1) // 2
+
+
+def spec_accept(sampled, drafts, span_cu, width, out=None):
+    """Draft acceptance for one verification pass, without the host.
+
+    sampled [R] int64: the token drawn from the target distribution at each
+    verification row. drafts [R] int64: the draft token checked at that
+    row, -1 at the last (bonus) row of a span. span_cu [S + 1] int32: span
+    s owns rows [cu[s], cu[s + 1]). width = W with 1 <= W <=
+    SPEC_MAX_DRAFT + 1. Per span, with m the longest prefix on which
+    sampled == drafts (the last row of a span always ends it):
+
+        emitted[s, :m + 1] = sampled[cu[s] : cu[s] + m + 1], rest -1
+        n_emit[s] = m + 1
+
+    A span that is empty, longer than W rows or not inside [0, R) gets
+    n_emit 0 and a row of -1, and indexes nothing. Returns (emitted [S, W]
+    int64, n_emit [S] int32): two sections of ONE int64 buffer
+    (spec_accept_sections), so that a single copy brings both to the host.
+    out = that buffer (contiguous int64, spec_accept_words(S, W) elements)
+    writes into an existing one. One launch, no host sync. Shape, dtype or
+    device mismatch raises ValueError. On the CPU this is
+    reference.spec_accept."""
+    if (sampled.dim() != 1 or sampled.numel() < 1
+            or sampled.dtype != torch.int64):
+        raise ValueError(
+            f"spec_accept: sampled must be int64 [R >= 1], got "
+            f"{sampled.dtype} {tuple(sampled.shape)}"
+        )
+    R = sampled.numel()
+    if R >= 1 << 31:
+        raise ValueError("spec_accept: need R < 2^31")
+    if drafts.dtype != torch.int64 or tuple(drafts.shape) != (R,):
+        raise ValueError(
+            f"spec_accept: drafts must be int64 ({R},), got {drafts.dtype} "
+            f"{tuple(drafts.shape)}"
+        )
+    if (span_cu.dim() != 1 or span_cu.dtype != torch.int32
+            or span_cu.numel() < 2):
+        raise ValueError(
+            f"spec_accept: span_cu must be int32 [S + 1 >= 2], got "
+            f"{span_cu.dtype} {tuple(span_cu.shape)}"
+        )
+    S = span_cu.numel() - 1
+    W = int(width)
+    if not 1 <= W <= SPEC_MAX_DRAFT + 1:
+        raise ValueError(
+            f"spec_accept: need 1 <= width <= {SPEC_MAX_DRAFT + 1}, got {W}"
+        )
+    if S >= 1 << 24:
+        raise ValueError("spec_accept: need S < 2^24")
+    words = spec_accept_words(S, W)
+    if out is None:
+        out = torch.empty(words, dtype=torch.int64, device=sampled.device)
+    elif (out.dtype != torch.int64 or tuple(out.shape) != (words,)
+            or not out.is_contiguous()):
+        raise ValueError(
+            f"spec_accept: out must be a contiguous int64 ({words},) "
+            f"tensor, got {out.dtype} {tuple(out.shape)}"
+        )
+    for name, t in (("drafts", drafts), ("span_cu", span_cu), ("out", out)):
+        if t.device != sampled.device:
+            raise ValueError(f"spec_accept: {name} is on {t.device}, "
+                             f"sampled on {sampled.device}")
+    emitted, n_emit = spec_accept_sections(out, S, W)
+    if sampled.is_cuda:
+        _require_native()
+        _C.spec_accept(emitted, n_emit, sampled.contiguous(),
+                       drafts.contiguous(), span_cu.contiguous())
+        return emitted, n_emit
+    return ref.spec_accept(sampled, drafts, span_cu, emitted, n_emit)
+
+
 compute_cos_sin_cache = ref.compute_cos_sin_cache

@@ -30,6 +30,7 @@ SOURCES = [
     "lora.hip",
     "sampling.hip",
     "penalties.hip",
+    "spec_verify.hip",
 ]
 
 

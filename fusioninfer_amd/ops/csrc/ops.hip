@@ -62,6 +62,11 @@ void launch_apply_penalties(float*, const int*, const int*, const float*, int,
                             int, int, hipStream_t);
 void launch_penalty_counts_add(int*, const int*, const int64_t*, int, int,
                                int, hipStream_t);
+void launch_apply_penalties_spec(float*, const int*, const int*, const float*,
+                                 const int64_t*, int, int, int, int,
+                                 hipStream_t);
+void launch_spec_accept(int64_t*, int*, const int64_t*, const int64_t*,
+                        const int*, int, int, int, hipStream_t);
 
 }  // namespace fi
 
@@ -717,6 +722,72 @@ void penalty_counts_add(at::Tensor counts, at::Tensor slot_ids,
       current_stream());
 }
 
+void apply_penalties_spec(at::Tensor logits, at::Tensor counts,
+                          at::Tensor slot_ids, at::Tensor params,
+                          at::Tensor extra) {
+  TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == at::kFloat &&
+              logits.is_contiguous() && logits.dim() == 2,
+              "apply_penalties_spec: logits must be a contiguous [R, V] fp32 "
+              "GPU tensor");
+  const int64_t T = logits.size(0);
+  const int64_t V = logits.size(1);
+  // T is the grid's y extent
+  TORCH_CHECK(T >= 1 && T <= 65535 && V >= 1 && V < (1LL << 30),
+              "apply_penalties_spec: need 1 <= R <= 65535 and 1 <= V < 2^30");
+  TORCH_CHECK(counts.is_cuda() && counts.scalar_type() == at::kInt &&
+              counts.is_contiguous() && counts.dim() == 2 &&
+              counts.size(0) >= 1 && counts.size(0) < (1LL << 31) &&
+              counts.size(1) == V,
+              "apply_penalties_spec: counts must be a contiguous [S >= 1, V] "
+              "int32 GPU tensor");
+  TORCH_CHECK(slot_ids.is_cuda() && slot_ids.scalar_type() == at::kInt &&
+              slot_ids.is_contiguous() && slot_ids.numel() == T,
+              "apply_penalties_spec: bad slot_ids");
+  TORCH_CHECK(params.is_cuda() && params.scalar_type() == at::kFloat &&
+              params.is_contiguous() && params.numel() == 4 * T,
+              "apply_penalties_spec: bad params");
+  // E bounds the kernel's LDS copy of a row's ids
+  TORCH_CHECK(extra.is_cuda() && extra.scalar_type() == at::kLong &&
+              extra.is_contiguous() && extra.dim() == 2 &&
+              extra.size(0) == T && extra.size(1) >= 1 && extra.size(1) <= 16,
+              "apply_penalties_spec: extra must be a contiguous [R, 1 <= E "
+              "<= 16] int64 GPU tensor");
+  fi::launch_apply_penalties_spec(
+      logits.data_ptr<float>(), counts.data_ptr<int>(),
+      slot_ids.data_ptr<int>(), params.data_ptr<float>(),
+      extra.data_ptr<int64_t>(), static_cast<int>(T), static_cast<int>(V),
+      static_cast<int>(counts.size(0)), static_cast<int>(extra.size(1)),
+      current_stream());
+}
+
+void spec_accept(at::Tensor emitted, at::Tensor n_emit, at::Tensor sampled,
+                 at::Tensor drafts, at::Tensor span_cu) {
+  TORCH_CHECK(emitted.is_cuda() && emitted.scalar_type() == at::kLong &&
+              emitted.is_contiguous() && emitted.dim() == 2 &&
+              emitted.size(0) >= 1 && emitted.size(0) < (1LL << 24) &&
+              emitted.size(1) >= 1 && emitted.size(1) <= 17,
+              "spec_accept: emitted must be a contiguous [1 <= S < 2^24, "
+              "1 <= W <= 17] int64 GPU tensor");
+  const int64_t S = emitted.size(0);
+  const int64_t R = sampled.numel();
+  TORCH_CHECK(R >= 1 && R < (1LL << 31), "spec_accept: need 1 <= R < 2^31");
+  auto check = [&](const at::Tensor& t, at::ScalarType ty, int64_t n,
+                   const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == ty && t.is_contiguous() &&
+                    t.dim() == 1 && t.numel() == n,
+                "spec_accept: bad ", name);
+  };
+  check(n_emit, at::kInt, S, "n_emit");
+  check(sampled, at::kLong, R, "sampled");
+  check(drafts, at::kLong, R, "drafts");
+  check(span_cu, at::kInt, S + 1, "span_cu");
+  fi::launch_spec_accept(
+      emitted.data_ptr<int64_t>(), n_emit.data_ptr<int>(),
+      sampled.data_ptr<int64_t>(), drafts.data_ptr<int64_t>(),
+      span_cu.data_ptr<int>(), static_cast<int>(R), static_cast<int>(S),
+      static_cast<int>(emitted.size(1)), current_stream());
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -769,4 +840,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "histogram (in-place on logits)");
   m.def("penalty_counts_add", &penalty_counts_add,
         "counts[slot_ids[i], token_ids[i]] += 1 (integer atomics)");
+  m.def("apply_penalties_spec", &apply_penalties_spec,
+        "apply_penalties for speculative verification rows: the histogram "
+        "plus up to 16 draft ids per row (in-place on logits)");
+  m.def("spec_accept", &spec_accept,
+        "longest accepted draft prefix plus the corrected token per "
+        "verification span");
 }

@@ -541,17 +541,41 @@ def apply_penalties(logits, counts, slot_ids, params):
     for t, slot in enumerate(slot_ids.tolist()):
         if slot < 0 or slot >= S:
             continue
-        rp, _, presence, frequency = params[t].tolist()
-        uniq = counts[slot].nonzero().flatten()
-        c = counts[slot][uniq]
-        row = logits[t]
-        if rp != 1.0:
-            vals = row[uniq]
-            row[uniq] = torch.where(vals > 0, vals / rp, vals * rp)
-        if presence != 0.0:
-            row[uniq] -= presence
-        if frequency != 0.0:
-            row[uniq] -= frequency * c.to(row.dtype)
+        _penalise_row(logits[t], counts[slot], params[t].tolist())
+    return logits
+
+
+def _penalise_row(row, hist, param):
+    """The sampler's penalty ops on one logits row, for the tokens whose
+    count in hist [V] is nonzero."""
+    rp, _, presence, frequency = param
+    uniq = hist.nonzero().flatten()
+    c = hist[uniq]
+    if rp != 1.0:
+        vals = row[uniq]
+        row[uniq] = torch.where(vals > 0, vals / rp, vals * rp)
+    if presence != 0.0:
+        row[uniq] -= presence
+    if frequency != 0.0:
+        row[uniq] -= frequency * c.to(row.dtype)
+
+
+def apply_penalties_spec(logits, counts, slot_ids, params, extra):
+    """Reference of the speculative penalty kernel, in place on logits
+    [R, V] fp32: apply_penalties with, per row, the histogram
+    counts[slot_ids[r]] plus one count for every id of extra[r] ([E] int64)
+    that lies in [0, V); other ids (the -1 padding included) are ignored.
+    counts itself is not changed."""
+    S, V = counts.shape
+    ids = extra.tolist()
+    for t, slot in enumerate(slot_ids.tolist()):
+        if slot < 0 or slot >= S:
+            continue
+        hist = counts[slot].clone()
+        for tok in ids[t]:
+            if 0 <= tok < V:
+                hist[tok] += 1
+        _penalise_row(logits[t], hist, params[t].tolist())
     return logits
 
 
@@ -612,3 +636,31 @@ def token_logprobs(logits, token_ids, num_top, out):
             top_ids[t, :k] = idx.to(top_ids.dtype)
             top_lp[t, :k] = lp[idx]
     return chosen, top_ids, top_lp
+
+
+# ------------------------------------------------- speculative verification
+
+def spec_accept(sampled, drafts, span_cu, emitted, n_emit):
+    """Reference of the spec_accept kernel and its CPU implementation.
+
+    sampled / drafts [R] int64, span_cu [S + 1] int32, emitted [S, W] int64
+    and n_emit [S] int32 written in place and returned. Span s owns rows
+    [cu[s], cu[s + 1]); it emits its samples up to and including the first
+    row whose sample differs from the draft checked there, the last row of
+    the span ending it in any case. Unused columns hold -1. An empty span,
+    one longer than W or one that leaves [0, R) emits nothing."""
+    R = sampled.numel()
+    S, W = emitted.shape
+    tok, dr, cu = sampled.tolist(), drafts.tolist(), span_cu.tolist()
+    emitted.fill_(-1)
+    for s in range(S):
+        lo, hi = cu[s], cu[s + 1]
+        n = 0
+        if 0 <= lo < hi <= R and hi - lo <= W:
+            for r in range(lo, hi):
+                emitted[s, n] = tok[r]
+                n += 1
+                if r == hi - 1 or tok[r] != dr[r]:
+                    break
+        n_emit[s] = n
+    return emitted, n_emit

@@ -79,7 +79,8 @@ def parse_args(argv=None):
     p.add_argument("--speculative-config", type=str, default=None,
                    help='JSON: {"method": "ngram", '
                         '"num_speculative_tokens": 4, '
-                        '"prompt_lookup_max": 4, "prompt_lookup_min": 2}')
+                        '"prompt_lookup_max": 4, "prompt_lookup_min": 2, '
+                        '"sampled_verify": true}')
     p.add_argument("--api-key", default=None,
                    help="bearer token required on every endpoint except "
                         "/health and /metrics (vLLM --api-key)")
@@ -133,6 +134,7 @@ def build_engine_config(args):
             ),
             model=raw.get("model"),
             draft_gpu_blocks=raw.get("draft_gpu_blocks"),
+            sampled_verify=bool(raw.get("sampled_verify", True)),
         )
     return EngineConfig(
         model=mc,

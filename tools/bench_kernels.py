@@ -2,7 +2,8 @@
 
 Usage: python tools/bench_kernels.py
            [prefill|decode|elementwise|lora|sampling|sampling_e2e|penalties|
-            penalties_e2e|logprobs|logprobs_e2e|all]
+            penalties_e2e|logprobs|logprobs_e2e|spec_verify|
+            spec_sampled_e2e|all]
 Prints per-shape timing + achieved TFLOP/s (attention) or GB/s (memory ops).
 """
 
@@ -645,6 +646,145 @@ def bench_logprobs_e2e(runs=3):
         torch.cuda.empty_cache()
 
 
+def bench_spec_verify():
+    """Speculative verification at V = 151936: Sampler.verify_drafts
+    (penalties + draw + acceptance + histogram update + logprobs on the
+    device, seeded sampled penalised spans of 1 + 4 rows with logprobs=2)
+    against the host argmax loop the greedy-only path runs on the same
+    number of rows (argmax(...).tolist() and the Python comparison). Both
+    end in the device-to-host copy the engine waits for, so the figure is
+    host wall time per call, synchronised; medians of 30 calls after 5."""
+    from fusioninfer_amd.engine.sampler import Sampler
+    from fusioninfer_amd.engine.sequence import SamplingParams, Sequence
+
+    V, k = 151936, 4
+    print("== speculative verification, V = 151936, spans of 1 + 4 rows ==")
+    print("| rows | spans | verify_drafts us | host argmax loop us |")
+    print("|---|---|---|---|")
+    g = torch.Generator().manual_seed(0)
+    for R in (5, 40, 160):
+        S = R // (k + 1)
+        logits = (torch.randn(R, V, generator=g) * 3).to("cuda:0")
+        sampler = Sampler(seed=1, device="cuda:0", backend="fused")
+        spans = []
+        for i in range(S):
+            seq = Sequence(
+                f"b{i}", torch.randint(0, V, (200,), generator=g).tolist(),
+                SamplingParams(temperature=0.8, top_k=50, top_p=0.9,
+                               seed=i, repetition_penalty=1.3,
+                               presence_penalty=0.5, frequency_penalty=0.2,
+                               logprobs=2))
+            spans.append(
+                (seq, torch.randint(0, V, (k,), generator=g).tolist()))
+
+        def device():
+            # in place on the logits: give every call the same input
+            sampler.verify_drafts(logits.clone(), spans)
+            for seq, _ in spans:
+                # the sequences do not grow here: tell the table so, or
+                # every call would rebuild the rows from the history
+                slot = sampler.penalty_table.slot_of(seq)
+                sampler.penalty_table._counted_len[slot] = seq.num_tokens
+
+        def host():
+            x = logits.clone()
+            greedy = x.argmax(dim=-1).tolist()
+            for i, (_, d) in enumerate(spans):
+                gs = greedy[i * (k + 1):(i + 1) * (k + 1)]
+                m = 0
+                while m < k and d[m] == gs[m]:
+                    m += 1
+
+        def wall(fn):
+            out = []
+            for i in range(35):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                if i >= 5:
+                    out.append((time.perf_counter() - t0) * 1e6)
+            return _median(out)
+
+        print(f"| {R} | {S} | {wall(device):.0f} | {wall(host):.0f} |",
+              flush=True)
+
+
+def bench_spec_sampled_e2e(runs=3):
+    """End-to-end: the 4-layer Qwen3-0.6B test engine, fused backend, n-gram
+    proposer (4 draft tokens, 1-gram lookup), 1 / 4 / 16 concurrent seeded
+    sampled requests on repetitive prompts with penalties that favour the
+    history, 64 tokens each, SpeculativeConfig.sampled_verify on and off
+    from one build, runs alternating. Wall ms per emitted token and the
+    acceptance rate. The weights are random: the acceptance rate says
+    nothing about real checkpoints."""
+    from fusioninfer_amd.config import (CacheConfig, EngineConfig,
+                                        SchedulerConfig)
+    from fusioninfer_amd.engine.llm_engine import LLMEngine
+    from fusioninfer_amd.engine.sequence import SamplingParams
+    from fusioninfer_amd.engine.spec_decode import SpeculativeConfig
+    from fusioninfer_amd.models.registry import get_model_config
+
+    def engine(on):
+        mc = get_model_config("Qwen3-0.6B")
+        mc.num_layers = 4
+        cfg = EngineConfig(
+            model=mc,
+            cache=CacheConfig(num_gpu_blocks=2048),
+            scheduler=SchedulerConfig(
+                max_num_seqs=16, max_num_batched_tokens=4096,
+                max_model_len=512,
+            ),
+            seed=7,
+            sampler_backend="fused",
+            speculative=SpeculativeConfig(
+                num_speculative_tokens=4, prompt_lookup_min=1,
+                sampled_verify=on),
+        )
+        torch.manual_seed(0)
+        return LLMEngine(cfg, device="cuda:0")
+
+    engines = {True: engine(True), False: engine(False)}
+
+    def run(eng, n):
+        for i in range(n):
+            eng.add_request(
+                [11 + i, 13 + i, 17 + i] * 20,
+                SamplingParams(max_tokens=64, temperature=0.8, top_k=50,
+                               top_p=0.9, seed=100 + i,
+                               repetition_penalty=0.8,
+                               presence_penalty=-1.0,
+                               frequency_penalty=-0.5),
+            )
+        d0, a0 = eng.num_spec_draft_tokens, eng.num_spec_accepted_tokens
+        t0g = eng.num_generated_tokens
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        while eng.has_unfinished():
+            eng.step()
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        return (dt, eng.num_generated_tokens - t0g,
+                eng.num_spec_draft_tokens - d0,
+                eng.num_spec_accepted_tokens - a0)
+
+    print("== engine decode, seeded sampled requests under n-gram "
+          "speculation (4-layer Qwen3-0.6B, fused backend) ==")
+    print("| requests | sampled_verify | run | tokens | ms/token | drafted "
+          "| accepted | acceptance |")
+    print("|---|---|---|---|---|---|---|---|")
+    for n in (1, 4, 16):
+        for on in (True, False):
+            run(engines[on], n)  # untimed
+        for i in range(runs):
+            for on in (True, False):
+                dt, toks, drafted, acc = run(engines[on], n)
+                rate = f"{acc / drafted:.2f}" if drafted else "-"
+                print(f"| {n} | {on} | {i} | {toks} | "
+                      f"{dt / toks * 1e3:.3f} | {drafted} | {acc} | "
+                      f"{rate} |", flush=True)
+
+
 class _OneTarget:
     """Minimal stand-in for LoRASlots: one layer, one target."""
 
@@ -676,3 +816,7 @@ if __name__ == "__main__":
         bench_logprobs()
     if which in ("logprobs_e2e", "all"):
         bench_logprobs_e2e()
+    if which in ("spec_verify", "all"):
+        bench_spec_verify()
+    if which in ("spec_sampled_e2e", "all"):
+        bench_spec_sampled_e2e()

@@ -165,4 +165,11 @@ class EngineConfig:
     # Requests asking for more take the host path. device_logprobs=False
     # is the A/B switch back to the host path for all of them.
     device_logprobs: bool = True
+    # Fused backend only, opt-in: `logit_bias` and guided-decoding masks are
+    # applied by one HIP apply_logit_mods launch inside the sampling pass
+    # (packed masks and the bias entries ride in its parameter copy). A
+    # biased sequence then stays on the pipelined-decode chain, and biased
+    # and guided sequences draft under speculation. False keeps both on the
+    # host path in the engine loop.
+    device_logit_mods: bool = False
     enforce_eager: bool = False            # True disables hipGraph decode capture

@@ -92,7 +92,8 @@ class LLMEngine:
                                backend=cfg.sampler_backend,
                                penalty_slots=cfg.penalty_slots,
                                device_penalties=cfg.device_penalties,
-                               device_logprobs=cfg.device_logprobs)
+                               device_logprobs=cfg.device_logprobs,
+                               device_logit_mods=cfg.device_logit_mods)
         from fusioninfer_amd.engine.spec_decode import build_proposer
 
         if (cfg.speculative is not None
@@ -688,11 +689,18 @@ class LLMEngine:
         over emitted tokens unless their histogram lives on the device)
         and nothing extra is read back beyond what rides on the pinned
         copy of the sampled ids (logprobs of up to LOGPROBS_MAX_TOP
-        entries from the fused backend's kernel)."""
+        entries from the fused backend's kernel).
+
+        logit_bias is a constant of the request, so a biased sequence is
+        eligible once the sampler applies the bias itself
+        (device_logit_mods). A guided sequence never is: the mask of step
+        N + 1 is a function of token N, which the host must have seen and
+        fed to the grammar before it can pack that mask, and the chain
+        launches N + 1 before it reads N."""
         sp = s.sampling
         return (
             sp.guided is None
-            and not sp.logit_bias
+            and (not sp.logit_bias or self.sampler.device_logit_mods)
             and (sp.logprobs is None
                  or (self.sampler.device_logprobs
                      and device_logprobs_top(sp) >= 0))
@@ -837,10 +845,29 @@ class LLMEngine:
     def _sample_and_emit(self, sample_seqs, logits_f) -> List[RequestOutput]:
         """Regular sampling path: logits_f row i belongs to sample_seqs[i].
         Guided sequences get their grammar mask applied first; a sequence
-        whose grammar admits no token is finished without emitting."""
+        whose grammar admits no token is finished without emitting. With
+        the sampler's device_logit_mods, bias and mask are the sampler's
+        (one launch inside its pass); here only the host-side emptiness
+        flag of the packed mask is consulted, with no device sync."""
         outputs: List[RequestOutput] = []
         keep = []
+        on_device = self.sampler.device_logit_mods
         for i, s in enumerate(sample_seqs):
+            if on_device:
+                g = s.sampling.guided
+                if g is not None:
+                    try:
+                        fits = g.packed_allowed() is not None
+                    except ValueError:
+                        # grammar blow-up: fail THIS request only
+                        fits = False
+                    if not fits:
+                        s.finish_reason = s.finish_reason or "stop"
+                        self._finish_seq(s)
+                        outputs.append(RequestOutput(s, new_token_ids=[]))
+                        continue
+                keep.append(i)
+                continue
             if s.sampling.logit_bias:
                 V = logits_f.shape[1]
                 # drop out-of-vocab ids: a bad request must not raise a
@@ -973,6 +1000,14 @@ class LLMEngine:
             if self._device_verify:
                 # kernel contract of the verify pass
                 del d[ops.SPEC_MAX_DRAFT:]
+            g = s.sampling.guided
+            if d and g is not None:
+                # before any block is taken: keep the prefix that stays
+                # inside the grammar and short of its end, so that every
+                # verification row has a non-empty mask and the token that
+                # completes the grammar is a sampled one. An emptied draft
+                # goes through the regular sampler.
+                del d[g.valid_draft_len(d):]
             if d:
                 last_pos = s.num_tokens - 1 + len(d)
                 if bm.extra_blocks_for(s, last_pos) > bm.num_free():
@@ -986,12 +1021,15 @@ class LLMEngine:
         """Draft eligibility when Sampler.verify_drafts does the
         verification (fused backend): any temperature; penalties when the
         sequence holds a slot of the device penalty table or one is free;
-        logprobs when ops.token_logprobs serves them. Grammar masks,
-        logit_bias and prompt_logprobs stay outside."""
+        logprobs when ops.token_logprobs serves them; logit_bias and
+        grammar masks when the sampler applies them (device_logit_mods;
+        guided drafts are trimmed to the grammar in _propose_drafts).
+        prompt_logprobs stays outside."""
         sp = s.sampling
+        mods = self.sampler.device_logit_mods
         return (
-            sp.guided is None
-            and not sp.logit_bias
+            (sp.guided is None or mods)
+            and (not sp.logit_bias or mods)
             and sp.prompt_logprobs is None
             and (sp.logprobs is None
                  or (self.sampler.device_logprobs

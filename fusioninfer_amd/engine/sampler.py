@@ -60,6 +60,84 @@ def device_logprobs_top(sp) -> int:
     return k if k <= ops.LOGPROBS_MAX_TOP else -1
 
 
+def bias_arrays(sp, vocab_size: int):
+    """A request's logit_bias as (ids int32 [n], values fp32 [n]) tensors,
+    ids outside [0, vocab_size) dropped (a bad request is ignored, not an
+    error). Built once per SamplingParams and kept on it: the bias is a
+    constant of the request."""
+    hit = getattr(sp, "_bias_arrays", None)
+    if hit is not None and hit[0] == vocab_size:
+        return hit[1], hit[2]
+    items = [(t, v) for t, v in sp.logit_bias.items()
+             if 0 <= t < vocab_size]
+    ids = torch.tensor([t for t, _ in items], dtype=torch.int32)
+    vals = torch.tensor([v for _, v in items], dtype=torch.float32)
+    sp._bias_arrays = (vocab_size, ids, vals)
+    return ids, vals
+
+
+class LogitMods:
+    """The logit_bias entries and grammar masks of one sampling pass, as
+    ops.apply_logit_mods takes them, laid out for the pass's parameter
+    buffer (Sampler._pack_rows):
+
+        mask_ids [T] | masks [M, W]                      (with a mask)
+        bias_cu [T + 1] | bias_ids [B] | bias_vals [B]   (with a bias)
+
+    Rows in the same grammar state share one mask. `offset` is the first
+    word of this section in the buffer, set by _pack_rows."""
+
+    def __init__(self, T, V, mask_ids, masks, bias_cu, bias_ids, bias_vals):
+        self.T, self.V, self.W = T, V, (V + 31) // 32
+        self.mask_ids = mask_ids  # list of int, or None
+        self.masks = masks  # list of int32 [W] CPU tensors
+        self.bias_cu = bias_cu  # list of int, or None
+        self.bias_ids = bias_ids  # list of int32 tensors, one per biased row
+        self.bias_vals = bias_vals
+        self.B = bias_cu[-1] if bias_cu is not None else 0
+        self.words = 0
+        if mask_ids is not None:
+            self.words += T + len(masks) * self.W
+        if bias_cu is not None:
+            self.words += T + 1 + 2 * self.B
+        self.offset = None
+
+    def fill(self, host: torch.Tensor) -> None:
+        p, T = self.offset, self.T
+        if self.mask_ids is not None:
+            host[p:p + T].copy_(torch.tensor(self.mask_ids, dtype=torch.int32))
+            p += T
+            for m in self.masks:
+                host[p:p + self.W].copy_(m)
+                p += self.W
+        if self.bias_cu is not None:
+            host[p:p + T + 1].copy_(
+                torch.tensor(self.bias_cu, dtype=torch.int32))
+            p += T + 1
+            if self.B:
+                host[p:p + self.B].copy_(torch.cat(self.bias_ids))
+                host[p + self.B:p + 2 * self.B].view(torch.float32).copy_(
+                    torch.cat(self.bias_vals))
+
+    def apply(self, logits: torch.Tensor, dev: torch.Tensor) -> None:
+        """One ops.apply_logit_mods launch on views of the device copy."""
+        from fusioninfer_amd import ops
+
+        p, T = self.offset, self.T
+        args = [None] * 5
+        if self.mask_ids is not None:
+            M = len(self.masks)
+            args[0] = dev[p:p + T]
+            args[1] = dev[p + T:p + T + M * self.W].view(M, self.W)
+            p += T + M * self.W
+        if self.bias_cu is not None:
+            B = self.B
+            args[2] = dev[p:p + T + 1]
+            args[3] = dev[p + T + 1:p + T + 1 + B]
+            args[4] = dev[p + T + 1 + B:p + T + 1 + 2 * B].view(torch.float32)
+        ops.apply_logit_mods(logits, *args)
+
+
 class DeviceLogprobs:
     """ops.token_logprobs outputs of one step in ONE int32 buffer, so that
     a single copy brings them to the host: chosen [T] fp32 | top_ids [T, W]
@@ -202,7 +280,8 @@ class Sampler:
     def __init__(self, seed: int = 0, device: str = "cpu",
                  backend: str = "torch", penalty_slots: int = 64,
                  device_penalties: bool = True,
-                 device_logprobs: bool = True):
+                 device_logprobs: bool = True,
+                 device_logit_mods: bool = False):
         if backend not in BACKENDS:
             raise ValueError(
                 f"sampler backend must be one of {BACKENDS}, got {backend!r}"
@@ -217,6 +296,10 @@ class Sampler:
             self.penalty_table = PenaltyTable(penalty_slots, device)
         # fused backend: logprobs from ops.token_logprobs, no host loop
         self.device_logprobs = backend == "fused" and device_logprobs
+        # fused backend, opt-in: logit_bias and grammar masks from one
+        # ops.apply_logit_mods launch inside the sampling pass; the engine
+        # then applies neither on the host
+        self.device_logit_mods = backend == "fused" and device_logit_mods
         self.generator = None
         if device != "cpu":
             self.generator = torch.Generator(device=device)
@@ -242,6 +325,46 @@ class Sampler:
     def release_penalty_slot(self, seq: Sequence) -> None:
         if self.penalty_table is not None:
             self.penalty_table.release(seq)
+
+    def _gather_logit_mods(self, rows, V: int):
+        """The one place that turns requests into ops.apply_logit_mods
+        input, for the plain step and for speculative verification. rows:
+        (sequence, grammar state or None) per logits row; the state is the
+        cursor's for a plain step and the walked-ahead one for row j of a
+        span. Returns a LogitMods, or None when the switch is off or no row
+        has a mask or an in-vocabulary bias entry (then nothing is
+        allocated, copied or launched for it). An empty mask is the
+        engine's business (it finishes such a request before sampling)."""
+        if not self.device_logit_mods or not any(
+            st is not None or s.sampling.logit_bias for s, st in rows
+        ):
+            return None
+        mask_ids, masks, index = [], [], {}
+        cu, ids, vals = [0], [], []
+        for s, st in rows:
+            mid = -1
+            if st is not None:
+                words, _ = s.sampling.guided.cache.packed_mask(st)
+                mid = index.get(id(words))
+                if mid is None:
+                    mid = index[id(words)] = len(masks)
+                    masks.append(words)
+            mask_ids.append(mid)
+            n = 0
+            if s.sampling.logit_bias:
+                b_ids, b_vals = bias_arrays(s.sampling, V)
+                n = b_ids.numel()
+                if n:
+                    ids.append(b_ids)
+                    vals.append(b_vals)
+            cu.append(cu[-1] + n)
+        if not masks:
+            mask_ids = None
+        if cu[-1] == 0:
+            cu = None
+        if mask_ids is None and cu is None:
+            return None
+        return LogitMods(len(rows), V, mask_ids, masks, cu, ids, vals)
 
     def _apply_penalties(self, logits: torch.Tensor, seqs: List[Sequence]):
         """repetition / presence / frequency penalties on already-emitted
@@ -296,9 +419,17 @@ class Sampler:
             _has_penalties(s.sampling) for s in seqs
         ):
             slots = self.penalty_table.sync(seqs, logits.shape[-1])
-        if slots is None:
+        mods = None
+        if self.device_logit_mods:
+            mods = self._gather_logit_mods(
+                [(s, None if s.sampling.guided is None
+                  else s.sampling.guided.state) for s in seqs],
+                logits.shape[-1],
+            )
+        if slots is None and mods is None:
             logits = self._apply_penalties(logits, seqs)
-        return self._sample_fused(logits, seqs, slots, num_top)
+        # with mods the host penalties wait until bias and mask are in
+        return self._sample_fused(logits, seqs, slots, num_top, mods)
 
     def sample(self, logits: torch.Tensor, seqs: List[Sequence]) -> torch.Tensor:
         """logits: [S, V] fp32; returns [S] int64 token ids."""
@@ -389,7 +520,8 @@ class Sampler:
             sampled[rows] = draw
         return sampled
 
-    def _pack_rows(self, rows, slots=None, num_top=None, tail_words=0):
+    def _pack_rows(self, rows, slots=None, num_top=None, tail_words=0,
+                   mods=None):
         """The host side of one fused sampling pass: per-row parameters in
         ONE int32 buffer, so that a single copy takes them to the device.
         rows: (sequence, j) per logits row, j = tokens the row is ahead of
@@ -403,7 +535,10 @@ class Sampler:
             [8T, 13T)  only when a slot of `slots` is live: (rp, 1/rp,
                        presence, frequency) as [T, 4] fp32, then the slots
             + T        only with num_top: one int per row
-            + tail     tail_words more words for the caller, starting at an
+            + mods     only with `mods` (a LogitMods): its mask_ids, masks
+                       and bias CSR, mods.words words; mods.offset is set
+                       to the first of them
+            + tail    tail_words more words for the caller, starting at an
                        even word (int64 views are possible there)
 
         Returns (buffer, live, pen_words, tail); pen_words is 13 or 8, tail
@@ -411,7 +546,11 @@ class Sampler:
         T = len(rows)
         live = slots is not None and any(slot >= 0 for slot in slots)
         pen_words = 13 if live else 8
-        words = (pen_words + (1 if num_top is not None else 0)) * T
+        row_words = (pen_words + (1 if num_top is not None else 0)) * T
+        words = row_words
+        if mods is not None:
+            mods.offset = row_words
+            words += mods.words
         tail = words + (words & 1)
         temps, ks, ps, mps, rng = [], [], [], [], []
         for s, j in rows:
@@ -446,12 +585,14 @@ class Sampler:
             ).flatten())
             host[12 * T:13 * T].copy_(torch.tensor(slots, dtype=torch.int32))
         if num_top is not None:
-            host[pen_words * T:words].copy_(
+            host[pen_words * T:row_words].copy_(
                 torch.tensor(num_top, dtype=torch.int32))
+        if mods is not None:
+            mods.fill(host)
         return host, live, pen_words, tail
 
     def _sample_fused(self, logits: torch.Tensor, seqs: List[Sequence],
-                      slots=None, num_top=None):
+                      slots=None, num_top=None, mods=None):
         """One ops.sample_tokens call for the whole mixed batch. The per-row
         parameters are laid out in one host buffer of 8 int32 words per row
         (temperature | top_k | top_p | min_p | rng as 2 x int64) and reach
@@ -469,16 +610,25 @@ class Sampler:
         `num_top` (one int per row, see device_logprobs_top) adds one more
         word per row at the end of the buffer and one ops.token_logprobs
         launch after the draw, on the same logits and the sampled ids.
+
+        `mods` (_gather_logit_mods) appends the step's packed grammar masks
+        and logit_bias entries to the same buffer; one ops.apply_logit_mods
+        runs first, so penalties, the draw and the logprobs all see bias
+        and mask, in the order of the host path.
         Returns (sampled ids, DeviceLogprobs or None)."""
         from fusioninfer_amd import ops
 
         T = len(seqs)
         host, live, pen_words, _ = self._pack_rows(
-            [(s, 0) for s in seqs], slots, num_top)
+            [(s, 0) for s in seqs], slots, num_top, mods=mods)
         dev = host.to(logits.device)
         if logits.dtype != torch.float32:
             logits = logits.float()
         logits = logits.contiguous()
+        if mods is not None:
+            mods.apply(logits, dev)
+            if slots is None:
+                self._apply_penalties(logits, seqs)
         if slots is not None:
             for i, s in enumerate(seqs):
                 # a finished sequence's token is discarded: no host sync
@@ -509,7 +659,7 @@ class Sampler:
         buf = torch.empty(T * (1 + 2 * W), dtype=torch.int32,
                           device=logits.device)
         ops.token_logprobs(
-            logits, sampled, dev[pen_words * T:],
+            logits, sampled, dev[pen_words * T:(pen_words + 1) * T],
             out=DeviceLogprobs.sections(buf, T, W),
         )
         return sampled, DeviceLogprobs(buf, num_top, W)
@@ -541,6 +691,13 @@ class Sampler:
         _apply_penalties row by row. Logprobs come from one
         ops.token_logprobs launch over all rows, after penalties and before
         temperature.
+
+        With device_logit_mods, one ops.apply_logit_mods runs in front of
+        all that: every row of a biased span gets the bias, and row j of a
+        guided span the mask of the grammar state after drafts[:j]
+        (GuidedDecoder.walk; the draft must stay inside the grammar, which
+        the engine's trimming guarantees). Its input rides in the same
+        host-to-device copy.
 
         One host-to-device copy (parameters, drafts, span bounds), at most
         two back (emitted tokens + counts; the logprobs buffer). Returns
@@ -581,13 +738,31 @@ class Sampler:
                 num_top = [span_top[i] for i in range(S)
                            for _ in range(cu[i], cu[i + 1])]
 
+        mods = None
+        if self.device_logit_mods:
+            row_states = []
+            for seq, draft in spans:
+                g = seq.sampling.guided
+                if g is None:
+                    row_states.extend((seq, None) for _ in range(len(draft) + 1))
+                    continue
+                # row j: the state after drafts[:j], the cursor stays put
+                states = g.walk(draft)
+                if len(states) != len(draft) + 1:
+                    raise ValueError(
+                        f"verify_drafts: the draft of {seq.seq_id} leaves "
+                        f"its grammar at token {max(len(states) - 1, 0)}; "
+                        "trim it first (GuidedDecoder.valid_draft_len)")
+                row_states.extend((seq, st) for st in states)
+            mods = self._gather_logit_mods(row_states, V)
+
         live = any(slot >= 0 for slot in span_slots)
         # the caller's part of the buffer: drafts [R] int64 | extra [R, E]
         # int64 (live only) | span_cu [S + 1] | span slots [S] (live only)
         n_extra = 2 * R * E if live else 0
         tail_words = 2 * R + n_extra + (S + 1) + (S if live else 0)
         host, _, pen_words, tail = self._pack_rows(
-            rows, slots, num_top, tail_words)
+            rows, slots, num_top, tail_words, mods)
         drafts_h = host[tail:tail + 2 * R].view(torch.int64)
         drafts_h.fill_(-1)
         for i, (_, d) in enumerate(spans):
@@ -610,6 +785,9 @@ class Sampler:
         if logits.dtype != torch.float32:
             logits = logits.float()
         logits = logits.contiguous()
+        if mods is not None:
+            # bias and masks first, as on the host path
+            mods.apply(logits, dev)
         for i, (seq, d) in enumerate(spans):
             if penalised[i] and span_slots[i] < 0:
                 # no slot: the host ops, on the history as row j sees it

@@ -30,6 +30,7 @@ from __future__ import annotations
 import json
 from typing import Dict, List, Optional, Tuple
 
+import numpy as np
 import torch
 
 # =============================================================== regex AST
@@ -666,12 +667,11 @@ class GuidedMaskCache:
         self.grammar = grammar
         self.vocab = vocab
         self._masks: Dict[Tuple, torch.Tensor] = {}
+        self._packed: Dict[Tuple, Tuple[torch.Tensor, bool]] = {}
 
-    def mask(self, state, device) -> torch.Tensor:
-        key = (self.grammar.signature(state), str(device))
-        m = self._masks.get(key)
-        if m is not None:
-            return m
+    def _allowed_ids(self, state) -> List[int]:
+        """Token ids the grammar admits in `state` (pruned DFS over the
+        vocabulary trie); the one source of mask() and packed_mask()."""
         allowed: List[int] = []
         g = self.grammar
 
@@ -689,12 +689,42 @@ class GuidedMaskCache:
             nxt = g.step(state, ch)
             if nxt is not None:
                 dfs(child, nxt)
+        return allowed
+
+    def mask(self, state, device) -> torch.Tensor:
+        key = (self.grammar.signature(state), str(device))
+        m = self._masks.get(key)
+        if m is not None:
+            return m
+        allowed = self._allowed_ids(state)
         m = torch.zeros(self.vocab.vocab_size, dtype=torch.bool)
         if allowed:
             m[torch.tensor(allowed, dtype=torch.long)] = True
         m = m.to(device)
         self._masks[key] = m
         return m
+
+    def packed_mask(self, state) -> Tuple[torch.Tensor, bool]:
+        """The mask of `state` as (int32 [ceil(V / 32)] CPU tensor, nonempty):
+        bit (v & 31) of word (v >> 5) set means token v is allowed, the
+        input format of ops.apply_logit_mods; bits at positions >= V are 0.
+        Cached by state signature (the same objects come back), so the
+        host knows whether a state admits a token without a device sync,
+        and a step moves V / 8 bytes per distinct state instead of keeping
+        a bool[V] per state on the device."""
+        key = self.grammar.signature(state)
+        hit = self._packed.get(key)
+        if hit is not None:
+            return hit
+        allowed = self._allowed_ids(state)
+        V = self.vocab.vocab_size
+        bits = np.zeros(((V + 31) // 32) * 32, dtype=np.uint8)
+        if allowed:
+            bits[np.asarray(allowed, dtype=np.int64)] = 1
+        words = np.packbits(bits, bitorder="little").view("<i4")
+        hit = (torch.from_numpy(words), bool(allowed))
+        self._packed[key] = hit
+        return hit
 
 
 # ============================================================ GBNF grammar
@@ -1011,6 +1041,70 @@ class GuidedDecoder:
             return True
         g = self.cache.grammar
         return g.is_complete(self.state) and not g.can_extend(self.state)
+
+    def packed_allowed(self) -> Optional[torch.Tensor]:
+        """allowed_mask() in the packed form of GuidedMaskCache.packed_mask
+        (int32 CPU words), None when no token fits; the emptiness is known
+        on the host, nothing is synchronised."""
+        if self.dead:
+            return None
+        words, nonempty = self.cache.packed_mask(self.state)
+        return words if nonempty else None
+
+    def walk(self, tokens) -> list:
+        """Grammar states along `tokens` without moving the cursor: the
+        state before each token and the one after the last, so walk([])
+        is [state] and the result has 1 + (tokens that the grammar
+        survived) entries. It ends early where a token kills the grammar,
+        and a ValueError of the grammar (state-explosion caps) ends it at
+        that point instead of propagating. Empty for a dead decoder."""
+        if self.dead:
+            return []
+        g = self.cache.grammar
+        strings = self.cache.vocab.strings
+        states = [self.state]
+        s = self.state
+        for tok in tokens:
+            if not 0 <= tok < len(strings):
+                break
+            try:
+                for ch in strings[tok]:
+                    s = g.step(s, ch)
+                    if s is None:
+                        break
+            except ValueError:
+                break
+            if s is None:
+                break
+            states.append(s)
+        return states
+
+    def valid_draft_len(self, draft) -> int:
+        """How many leading tokens of a speculative draft may be verified:
+        token j survives only if the mask of the state after draft[:j]
+        allows it AND the state after it still has a non-empty mask and is
+        not terminal. Everything from the first failure on is dropped, so
+        no verification row of the kept span has an empty mask, and a token
+        that completes the grammar is always sampled, never an accepted
+        draft. The cursor is not moved."""
+        states = self.walk(draft)
+        cache, g = self.cache, self.cache.grammar
+        keep = 0
+        for j in range(len(states) - 1):
+            tok = draft[j]
+            try:
+                words, _ = cache.packed_mask(states[j])
+                if not (int(words[tok >> 5]) >> (tok & 31)) & 1:
+                    break
+                nxt = states[j + 1]
+                if not cache.packed_mask(nxt)[1]:
+                    break
+                if g.is_complete(nxt) and not g.can_extend(nxt):
+                    break
+            except ValueError:
+                break
+            keep = j + 1
+        return keep
 
 
 # ============================================================== factory

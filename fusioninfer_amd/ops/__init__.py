@@ -1003,4 +1003,103 @@ def spec_accept(sampled, drafts, span_cu, width, out=None):
     return ref.spec_accept(sampled, drafts, span_cu, emitted, n_emit)
 
 
+# ------------------------------------------------ logit_bias / grammar masks
+
+def apply_logit_mods(logits, mask_ids=None, masks=None, bias_cu=None,
+                     bias_ids=None, bias_vals=None):
+    """logit_bias and packed grammar masks, in place on logits: bias, then
+    mask (the order of the engine's host path).
+
+    logits [T, V] fp32 contiguous. Either half may be absent (all of its
+    arguments None); with both absent nothing is launched.
+
+    Mask half: masks [M, W] int32 contiguous with W = ceil(V / 32); bit
+    (v & 31) of word (v >> 5) set means token v is allowed; bits at
+    positions >= V are ignored. mask_ids [T] int32 names each row's mask; an
+    id outside [0, M) (canonically -1) means no mask and is never used as
+    an index. Every disallowed element of a masked row becomes exactly -inf,
+    whatever it held (NaN included) and whatever its bias.
+
+    Bias half, CSR: bias_cu [T + 1] int32, bias_ids [B] int32, bias_vals [B]
+    fp32. Row t does x = x + bias_vals[e] (one fp32 add, the host path's
+    indexed add) for e in [bias_cu[t], bias_cu[t + 1]), clamped to [0, B).
+    An id outside [0, V) is skipped and never used as an index. Ids within a
+    row must be distinct; the host guarantees that (they are dict keys), the
+    kernel does not check it, and a duplicate would make two threads race on
+    one element.
+
+    Allowed elements without a bias entry and rows with neither a mask nor
+    a bias are left bit-for-bit untouched (not stored to). No element has
+    two writers, so the result does not depend on workgroup order. One
+    launch, static grid, no workspace, no host sync. Shape, dtype, device or
+    contiguity mismatch raises ValueError. On the CPU this is
+    reference.apply_logit_mods."""
+    op = "apply_logit_mods"
+    if logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1:
+        raise ValueError(
+            f"{op}: logits must be [T >= 1, V >= 1], got "
+            f"{tuple(logits.shape)}"
+        )
+    T, V = logits.shape
+    if logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise ValueError(
+            f"{op}: logits must be contiguous fp32 (the op works in place), "
+            f"got {logits.dtype} strides {logits.stride()}"
+        )
+    if T > PENALTY_MAX_ROWS or V >= 1 << 30:
+        raise ValueError(
+            f"{op}: need T <= {PENALTY_MAX_ROWS} and V < 2^30, got T={T} "
+            f"V={V}"
+        )
+    has_mask = mask_ids is not None or masks is not None
+    has_bias = any(x is not None for x in (bias_cu, bias_ids, bias_vals))
+    if has_mask and (mask_ids is None or masks is None):
+        raise ValueError(f"{op}: mask_ids and masks come together")
+    if has_bias and any(x is None for x in (bias_cu, bias_ids, bias_vals)):
+        raise ValueError(
+            f"{op}: bias_cu, bias_ids and bias_vals come together")
+    checks = []
+    if has_mask:
+        W = (V + 31) // 32
+        if (masks.dim() != 2 or masks.dtype != torch.int32
+                or masks.shape[0] < 1 or masks.shape[1] != W):
+            raise ValueError(
+                f"{op}: masks must be int32 [M >= 1, ceil(V / 32) = {W}], "
+                f"got {masks.dtype} {tuple(masks.shape)}"
+            )
+        checks += [("mask_ids", mask_ids, torch.int32, (T,)),
+                   ("masks", masks, torch.int32, tuple(masks.shape))]
+    if has_bias:
+        if bias_ids.dim() != 1 or bias_ids.numel() >= 1 << 30:
+            raise ValueError(
+                f"{op}: bias_ids must be [B < 2^30], got "
+                f"{tuple(bias_ids.shape)}"
+            )
+        B = bias_ids.numel()
+        checks += [("bias_cu", bias_cu, torch.int32, (T + 1,)),
+                   ("bias_ids", bias_ids, torch.int32, (B,)),
+                   ("bias_vals", bias_vals, torch.float32, (B,))]
+    for name, t, dtype, shape in checks:
+        if t.dtype != dtype or tuple(t.shape) != shape:
+            raise ValueError(
+                f"{op}: {name} must be {dtype} {shape}, got {t.dtype} "
+                f"{tuple(t.shape)}"
+            )
+        if t.device != logits.device:
+            raise ValueError(f"{op}: {name} is on {t.device}, logits on "
+                             f"{logits.device}")
+        if not t.is_contiguous():
+            raise ValueError(f"{op}: {name} must be contiguous, got strides "
+                             f"{t.stride()}")
+    if not checks:
+        return logits
+    if logits.is_cuda:
+        _require_native()
+        _C.apply_logit_mods(logits, mask_ids, masks, bias_cu, bias_ids,
+                            bias_vals)
+        return logits
+    return ref.apply_logit_mods(logits, mask_ids, masks, bias_cu, bias_ids,
+                                bias_vals)
+
+
 compute_cos_sin_cache = ref.compute_cos_sin_cache

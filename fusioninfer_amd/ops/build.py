@@ -31,6 +31,7 @@ SOURCES = [
     "sampling.hip",
     "penalties.hip",
     "spec_verify.hip",
+    "logit_mods.hip",
 ]
 
 

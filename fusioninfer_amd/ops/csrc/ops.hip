@@ -67,6 +67,9 @@ void launch_apply_penalties_spec(float*, const int*, const int*, const float*,
                                  hipStream_t);
 void launch_spec_accept(int64_t*, int*, const int64_t*, const int64_t*,
                         const int*, int, int, int, hipStream_t);
+void launch_apply_logit_mods(float*, const int*, const int*, const int*,
+                             const int*, const float*, int, int, int, int,
+                             int, hipStream_t);
 
 }  // namespace fi
 
@@ -788,6 +791,88 @@ void spec_accept(at::Tensor emitted, at::Tensor n_emit, at::Tensor sampled,
       static_cast<int>(emitted.size(1)), current_stream());
 }
 
+// Either half may be absent (both of its tensors undefined): mask_ids +
+// masks, or bias_cu + bias_ids + bias_vals.
+void apply_logit_mods(at::Tensor logits, c10::optional<at::Tensor> mask_ids,
+                      c10::optional<at::Tensor> masks,
+                      c10::optional<at::Tensor> bias_cu,
+                      c10::optional<at::Tensor> bias_ids,
+                      c10::optional<at::Tensor> bias_vals) {
+  TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == at::kFloat &&
+              logits.is_contiguous() && logits.dim() == 2,
+              "apply_logit_mods: logits must be a contiguous [T, V] fp32 GPU "
+              "tensor");
+  const int64_t T = logits.size(0);
+  const int64_t V = logits.size(1);
+  // T is the grid's y extent
+  TORCH_CHECK(T >= 1 && T <= 65535 && V >= 1 && V < (1LL << 30),
+              "apply_logit_mods: need 1 <= T <= 65535 and 1 <= V < 2^30");
+  const int64_t W = (V + 31) / 32;
+  const bool has_mask = mask_ids.has_value();
+  const bool has_bias = bias_cu.has_value();
+  TORCH_CHECK(masks.has_value() == has_mask,
+              "apply_logit_mods: mask_ids and masks come together");
+  TORCH_CHECK(bias_ids.has_value() == has_bias &&
+              bias_vals.has_value() == has_bias,
+              "apply_logit_mods: bias_cu, bias_ids and bias_vals come "
+              "together");
+  TORCH_CHECK(has_mask || has_bias,
+              "apply_logit_mods: neither a mask nor a bias given");
+  const int* mask_ids_p = nullptr;
+  const int* masks_p = nullptr;
+  int64_t M = 0;
+  if (has_mask) {
+    TORCH_CHECK(mask_ids->is_cuda() && mask_ids->scalar_type() == at::kInt &&
+                mask_ids->is_contiguous() && mask_ids->dim() == 1 &&
+                mask_ids->numel() == T,
+                "apply_logit_mods: mask_ids must be a contiguous [T] int32 "
+                "GPU tensor");
+    TORCH_CHECK(masks->is_cuda() && masks->scalar_type() == at::kInt &&
+                masks->is_contiguous() && masks->dim() == 2 &&
+                masks->size(0) >= 1 && masks->size(0) < (1LL << 31) &&
+                masks->size(1) == W,
+                "apply_logit_mods: masks must be a contiguous [M >= 1, "
+                "ceil(V / 32)] int32 GPU tensor");
+    M = masks->size(0);
+    mask_ids_p = mask_ids->data_ptr<int>();
+    masks_p = masks->data_ptr<int>();
+  }
+  const int* bias_cu_p = nullptr;
+  const int* bias_ids_p = nullptr;
+  const float* bias_vals_p = nullptr;
+  int64_t B = 0;
+  if (has_bias) {
+    TORCH_CHECK(bias_cu->is_cuda() && bias_cu->scalar_type() == at::kInt &&
+                bias_cu->is_contiguous() && bias_cu->dim() == 1 &&
+                bias_cu->numel() == T + 1,
+                "apply_logit_mods: bias_cu must be a contiguous [T + 1] "
+                "int32 GPU tensor");
+    B = bias_ids->numel();
+    // entry indices advance by up to 2^19 * 256 threads per step
+    TORCH_CHECK(bias_ids->is_cuda() && bias_ids->scalar_type() == at::kInt &&
+                bias_ids->is_contiguous() && bias_ids->dim() == 1 &&
+                B < (1LL << 30),
+                "apply_logit_mods: bias_ids must be a contiguous [B < 2^30] "
+                "int32 GPU tensor");
+    TORCH_CHECK(bias_vals->is_cuda() &&
+                bias_vals->scalar_type() == at::kFloat &&
+                bias_vals->is_contiguous() && bias_vals->dim() == 1 &&
+                bias_vals->numel() == B,
+                "apply_logit_mods: bias_vals must be a contiguous [B] fp32 "
+                "GPU tensor");
+    bias_cu_p = bias_cu->data_ptr<int>();
+    if (B > 0) {
+      bias_ids_p = bias_ids->data_ptr<int>();
+      bias_vals_p = bias_vals->data_ptr<float>();
+    }
+  }
+  fi::launch_apply_logit_mods(
+      logits.data_ptr<float>(), mask_ids_p, masks_p, bias_cu_p, bias_ids_p,
+      bias_vals_p, static_cast<int>(T), static_cast<int>(V),
+      static_cast<int>(M), static_cast<int>(W), static_cast<int>(B),
+      current_stream());
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -846,4 +931,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("spec_accept", &spec_accept,
         "longest accepted draft prefix plus the corrected token per "
         "verification span");
+  m.def("apply_logit_mods", &apply_logit_mods,
+        "logit_bias (CSR) and packed grammar masks, bias then mask "
+        "(in-place on logits)");
 }

@@ -592,6 +592,44 @@ def penalty_counts_add(counts, slot_ids, token_ids):
     return counts
 
 
+# ------------------------------------------------ logit_bias / grammar masks
+
+def unpack_mask(words, V):
+    """bool[V] of a packed mask [ceil(V / 32)] int32: bit (v & 31) of word
+    (v >> 5)."""
+    shifts = torch.arange(32, dtype=torch.int32, device=words.device)
+    bits = (words.unsqueeze(1) >> shifts) & 1
+    return bits.flatten()[:V].bool()
+
+
+def apply_logit_mods(logits, mask_ids, masks, bias_cu, bias_ids, bias_vals):
+    """Reference of the logit_mods kernel, in place on logits [T, V] fp32:
+    per row the ops of LLMEngine._sample_and_emit's host path, an indexed
+    add of the row's bias entries (ids outside [0, V) dropped) and then
+    masked_fill_(~allowed, -inf) with the row's unpacked mask. Either half
+    may be None. Rows whose mask id is outside [0, M) have no mask; bias_cu
+    is clamped to [0, B)."""
+    T, V = logits.shape
+    if bias_cu is not None:
+        B = bias_ids.numel()
+        cu = bias_cu.tolist()
+        for t in range(T):
+            lo, hi = max(cu[t], 0), min(cu[t + 1], B)
+            if lo >= hi:
+                continue
+            ids = bias_ids[lo:hi].long()
+            ok = (ids >= 0) & (ids < V)
+            if bool(ok.any()):
+                logits[t, ids[ok]] += bias_vals[lo:hi][ok]
+    if mask_ids is not None:
+        M = masks.shape[0]
+        for t, mid in enumerate(mask_ids.tolist()):
+            if 0 <= mid < M:
+                logits[t].masked_fill_(~unpack_mask(masks[mid], V),
+                                       float("-inf"))
+    return logits
+
+
 # ---------------------------------------------------------------- logprobs
 
 def token_logprobs(logits, token_ids, num_top, out):

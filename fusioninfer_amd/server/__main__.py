@@ -53,6 +53,11 @@ def parse_args(argv=None):
     p.add_argument("--no-device-logprobs", action="store_true",
                    help="fused sampler: compute logprobs on the host path "
                         "(such requests then leave pipelined decode)")
+    p.add_argument("--device-logit-mods", action="store_true",
+                   help="fused sampler: apply logit_bias and guided-decoding "
+                        "masks on the device (biased requests stay in "
+                        "pipelined decode; biased and guided requests draft "
+                        "under speculation)")
     p.add_argument("--kv-cache-dtype", choices=["auto", "fp8"], default="auto")
     p.add_argument("--swap-space", type=float, default=0.0,
                    help="GiB of CPU swap for preempted sequences (0=recompute)")
@@ -166,6 +171,7 @@ def build_engine_config(args):
         penalty_slots=args.penalty_slots,
         device_penalties=not args.no_device_penalties,
         device_logprobs=not args.no_device_logprobs,
+        device_logit_mods=args.device_logit_mods,
     )
 
 

@@ -3,7 +3,7 @@
 Usage: python tools/bench_kernels.py
            [prefill|decode|elementwise|lora|sampling|sampling_e2e|penalties|
             penalties_e2e|logprobs|logprobs_e2e|spec_verify|
-            spec_sampled_e2e|all]
+            spec_sampled_e2e|logit_mods|guided_spec_e2e|bias_pipelining|all]
 Prints per-shape timing + achieved TFLOP/s (attention) or GB/s (memory ops).
 """
 
@@ -785,6 +785,236 @@ def bench_spec_sampled_e2e(runs=3):
                       f"{rate} |", flush=True)
 
 
+def _wall_us(fn, n=30, warm=5):
+    out = []
+    for i in range(n + warm):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        if i >= warm:
+            out.append((time.perf_counter() - t0) * 1e6)
+    out.sort()
+    return out[len(out) // 2], out[0], out[-1]
+
+
+def bench_logit_mods():
+    """ops.apply_logit_mods plus the copy of its input to the device against
+    the engine's host path, V = 151936. Masks: every row masked, 4 distinct
+    masks of about 3 % allowed tokens; host path = per row the device-cached
+    bool[V] mask, bool(m.any()) and masked_fill_. Bias: every row with 300
+    entries; host path = per row a fresh torch.tensor(...) and an indexed
+    add. Wall time per call with a synchronize on both sides (the host path
+    synchronises by itself), median (min-max) of 30 after 5 warm-up calls;
+    'kernel us' is the device-event time of the launch alone."""
+    import numpy as np
+
+    V = 151936
+    W = (V + 31) // 32
+    g = torch.Generator().manual_seed(0)
+    bool_masks = [torch.rand(V, generator=g) < 0.03 for _ in range(4)]
+    packed = []
+    for m in bool_masks:
+        bits = torch.zeros(W * 32, dtype=torch.uint8)
+        bits[:V] = m
+        packed.append(torch.from_numpy(
+            np.packbits(bits.numpy(), bitorder="little").view("<i4")))
+    dev_masks = [m.cuda() for m in bool_masks]
+    bias_ids = torch.randperm(V, generator=g)[:300].tolist()
+    bias_vals = torch.randn(300, generator=g).tolist()
+    print("== logit_mods: apply_logit_mods + its input copy vs the host "
+          "path (V=151936) ==")
+    print("| config | T | bytes to device | device path us (min-max) | "
+          "kernel us | host path us (min-max) | host/device |")
+    print("|---|---|---|---|---|---|---|")
+    for T in (1, 8, 64, 256):
+        logits = torch.randn(T, V, device="cuda") * 4
+        # masks
+        host = torch.empty(T + 4 * W, dtype=torch.int32).pin_memory()
+        host[:T] = torch.arange(T, dtype=torch.int32) % 4
+        host[T:] = torch.cat(packed)
+        dev = host.cuda()
+
+        def dev_mask():
+            d = host.to("cuda", non_blocking=True)
+            ops.apply_logit_mods(logits, d[:T], d[T:].view(4, W))
+
+        def host_mask():
+            for t in range(T):
+                m = dev_masks[t % 4]
+                if bool(m.any()):
+                    logits[t].masked_fill_(~m, float("-inf"))
+
+        k_us = _median(_event_times_us(
+            lambda: ops.apply_logit_mods(logits, dev[:T],
+                                         dev[T:].view(4, W)), 40))
+        d_us, h_us = _wall_us(dev_mask), _wall_us(host_mask)
+        print(f"| masks | {T} | {host.numel() * 4} | {d_us[0]:.0f} "
+              f"({d_us[1]:.0f}-{d_us[2]:.0f}) | {k_us:.1f} | {h_us[0]:.0f} "
+              f"({h_us[1]:.0f}-{h_us[2]:.0f}) | {h_us[0] / d_us[0]:.1f}x |",
+              flush=True)
+        # bias
+        B = 300 * T
+        hostb = torch.empty(T + 1 + 2 * B, dtype=torch.int32).pin_memory()
+        hostb[:T + 1] = torch.arange(T + 1, dtype=torch.int32) * 300
+        hostb[T + 1:T + 1 + B] = torch.tensor(bias_ids * T,
+                                              dtype=torch.int32)
+        hostb[T + 1 + B:].view(torch.float32).copy_(
+            torch.tensor(bias_vals * T))
+        devb = hostb.cuda()
+
+        def split(d):
+            return dict(bias_cu=d[:T + 1], bias_ids=d[T + 1:T + 1 + B],
+                        bias_vals=d[T + 1 + B:].view(torch.float32))
+
+        def dev_bias():
+            ops.apply_logit_mods(
+                logits, **split(hostb.to("cuda", non_blocking=True)))
+
+        def host_bias():
+            for t in range(T):
+                logits[t, bias_ids] += torch.tensor(
+                    bias_vals, dtype=logits.dtype, device=logits.device)
+
+        logits.normal_()
+        k_us = _median(_event_times_us(
+            lambda: ops.apply_logit_mods(logits, **split(devb)), 40))
+        d_us, h_us = _wall_us(dev_bias), _wall_us(host_bias)
+        print(f"| bias | {T} | {hostb.numel() * 4} | {d_us[0]:.0f} "
+              f"({d_us[1]:.0f}-{d_us[2]:.0f}) | {k_us:.1f} | {h_us[0]:.0f} "
+              f"({h_us[1]:.0f}-{h_us[2]:.0f}) | {h_us[0] / d_us[0]:.1f}x |",
+              flush=True)
+
+
+def _mods_engine(mods, spec, max_seqs=16):
+    from fusioninfer_amd.config import (CacheConfig, EngineConfig,
+                                        SchedulerConfig)
+    from fusioninfer_amd.engine.llm_engine import LLMEngine
+    from fusioninfer_amd.engine.spec_decode import SpeculativeConfig
+    from fusioninfer_amd.models.registry import get_model_config
+
+    mc = get_model_config("Qwen3-0.6B")
+    mc.num_layers = 4
+    cfg = EngineConfig(
+        model=mc,
+        cache=CacheConfig(num_gpu_blocks=2048),
+        scheduler=SchedulerConfig(
+            max_num_seqs=max_seqs, max_num_batched_tokens=4096,
+            max_model_len=512,
+        ),
+        seed=7,
+        sampler_backend="fused",
+        device_logit_mods=mods,
+        speculative=SpeculativeConfig(
+            num_speculative_tokens=4, prompt_lookup_min=1) if spec else None,
+    )
+    torch.manual_seed(0)
+    return LLMEngine(cfg, device="cuda:0")
+
+
+def bench_guided_spec_e2e(runs=3):
+    """End-to-end: the 4-layer Qwen3-0.6B test engine, fused backend, one
+    token per byte, guided requests on a JSON-like regex with fixed keys
+    (three records), greedy, the prompt holding one record of that shape;
+    n-gram proposer with k = 4. 1 and 8 concurrent requests. Three engines
+    from one build, runs alternating: switch on + drafting, switch on
+    without drafting, switch off (the host mask path; with the switch off a
+    guided request never drafts, so that is the parent's behaviour with or
+    without a proposer). Tokens/s and the acceptance rate. The weights are
+    random: the free parts of the output (names, digits) are whatever the
+    model prefers, so the acceptance rate says nothing about real
+    checkpoints."""
+    from fusioninfer_amd.engine.sequence import SamplingParams
+    from fusioninfer_amd.guided import Vocabulary, build_guided
+
+    rec = r'\{"name": "[a-z]{4}", "id": [0-9]{3}, "active": (true|false)\}'
+    regex = rec + ", " + rec + ", " + rec
+    prompt = [ord(c) + 3 for c in
+              '{"name": "abcd", "id": 123, "active": true}, ']
+    engines = {
+        "on, drafting": _mods_engine(True, True),
+        "on, no drafting": _mods_engine(True, False),
+        "off (host masks)": _mods_engine(False, True),
+    }
+    vocab = Vocabulary(engines["on, drafting"].cfg.model.vocab_size,
+                       lambda t: chr(t - 3) if 3 <= t < 259 else "")
+
+    def run(eng, n):
+        for i in range(n):
+            eng.add_request(prompt, SamplingParams(
+                max_tokens=200, guided=build_guided("regex", regex, vocab)))
+        d0, a0 = eng.num_spec_draft_tokens, eng.num_spec_accepted_tokens
+        t0g, s0 = eng.num_generated_tokens, eng.num_steps
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        while eng.has_unfinished():
+            eng.step()
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        return (dt, eng.num_generated_tokens - t0g, eng.num_steps - s0,
+                eng.num_spec_draft_tokens - d0,
+                eng.num_spec_accepted_tokens - a0)
+
+    print("== guided requests under n-gram speculation (4-layer "
+          "Qwen3-0.6B, fused backend, JSON-like regex) ==")
+    print("| requests | device_logit_mods | run | tokens | steps | tokens/s "
+          "| drafted | accepted | acceptance |")
+    print("|---|---|---|---|---|---|---|---|---|")
+    for n in (1, 8):
+        for eng in engines.values():
+            run(eng, n)  # untimed
+        for i in range(runs):
+            for name, eng in engines.items():
+                dt, toks, steps, drafted, acc = run(eng, n)
+                rate = f"{acc / drafted:.2f}" if drafted else "-"
+                print(f"| {n} | {name} | {i} | {toks} | {steps} | "
+                      f"{toks / dt:.0f} | {drafted} | {acc} | {rate} |",
+                      flush=True)
+
+
+def bench_bias_pipelining(runs=3):
+    """64 plain greedy sequences plus one with a logit_bias, 64 tokens each,
+    4-layer Qwen3-0.6B test engine, fused backend, device_logit_mods off and
+    on: wall ms per engine step and the share of pipelined steps."""
+    from fusioninfer_amd.engine.sequence import SamplingParams
+
+    print("== 64 greedy sequences + 1 biased one (4-layer Qwen3-0.6B, "
+          "fused backend) ==")
+    print("| device_logit_mods | run | steps | ms/step | pipelined steps | "
+          "share |")
+    print("|---|---|---|---|---|---|")
+    # max_num_seqs is a decode-graph bucket: the static decode buffers are
+    # sized by the largest bucket below it
+    engines = {on: _mods_engine(on, False, max_seqs=128)
+               for on in (False, True)}
+
+    def run(eng):
+        for i in range(65):
+            eng.add_request(
+                [(7 * i + j) % 1000 + 10 for j in range(32)],
+                SamplingParams(
+                    max_tokens=64,
+                    logit_bias={t: 2.0 for t in range(500, 800)}
+                    if i == 64 else None),
+            )
+        steps0, async0 = eng.num_steps, eng.num_async_steps
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        while eng.has_unfinished():
+            eng.step()
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        return dt, eng.num_steps - steps0, eng.num_async_steps - async0
+
+    for eng in engines.values():
+        run(eng)
+    for i in range(runs):
+        for on, eng in engines.items():
+            dt, steps, n_async = run(eng)
+            print(f"| {on} | {i} | {steps} | {dt / steps * 1e3:.2f} | "
+                  f"{n_async} | {n_async / steps:.2f} |", flush=True)
+
+
 class _OneTarget:
     """Minimal stand-in for LoRASlots: one layer, one target."""
 
@@ -820,3 +1050,9 @@ if __name__ == "__main__":
         bench_spec_verify()
     if which in ("spec_sampled_e2e", "all"):
         bench_spec_sampled_e2e()
+    if which in ("logit_mods", "all"):
+        bench_logit_mods()
+    if which in ("guided_spec_e2e", "all"):
+        bench_guided_spec_e2e()
+    if which in ("bias_pipelining", "all"):
+        bench_bias_pipelining()

@@ -170,6 +170,10 @@ class LLMEngine:
         assert self.cfg.model.quantization != "fp8", (
             "LoRA is not supported with --quantization fp8"
         )
+        # mxfp4 layers have no bf16 weight for forward_with_lora to use
+        assert self.cfg.model.quantization != "mxfp4", (
+            "LoRA is not supported with --quantization mxfp4"
+        )
         if (self.cfg.parallel.tensor_parallel_size
                 * self.cfg.parallel.pipeline_parallel_size) > 1:
             assert self.is_driver

@@ -40,6 +40,10 @@ class ModelRunner:
         self.is_cuda = self.device.type == "cuda"
         mc = cfg.model
         torch.manual_seed(cfg.seed)
+        if mc.quantization == "mxfp4" and mc.is_moe:
+            # the experts are ~90 % of an MoE model's weights and would
+            # stay bf16: refuse rather than mislead
+            raise ValueError("mxfp4 does not cover MoE experts yet")
         fp8_ckpt = False
         if mc.model_path:
             from fusioninfer_amd.models.weight_loader import checkpoint_is_fp8
@@ -73,7 +77,16 @@ class ModelRunner:
 
                 n = convert_linear_to_fp8(self.model)
                 assert n > 0
-        if mc.quantization not in (None, "fp8"):
+            elif mc.quantization == "mxfp4":
+                # weight-only: bf16 weights (checkpoint or random init) are
+                # quantized here, activations stay bf16
+                from fusioninfer_amd.quantization import (
+                    convert_linear_to_mxfp4,
+                )
+
+                n = convert_linear_to_mxfp4(self.model)
+                assert n > 0
+        if mc.quantization not in (None, "fp8", "mxfp4"):
             raise ValueError(f"unknown quantization {mc.quantization!r}")
         if self.is_cuda and os.environ.get(
                 "FI_MOE_KEEP_UNPACKED", "0") != "1":
@@ -102,7 +115,7 @@ class ModelRunner:
         self.num_lora_eager_steps = 0    # decode steps with adapters run eager
         self.num_lora_slot_steps = 0     # steps (any kind) on the slot kernels
         self.num_lora_loop_steps = 0     # steps on the per-adapter torch loop
-        if cfg.enable_lora and mc.quantization != "fp8":
+        if cfg.enable_lora and mc.quantization not in ("fp8", "mxfp4"):
             from fusioninfer_amd.lora import LoRASlots
 
             self.lora_slots = LoRASlots(

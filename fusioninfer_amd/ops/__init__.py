@@ -595,6 +595,125 @@ def lora_apply(out, x, slot_ids, a_stack, b_stack, scales):
     return ref.lora_apply(out, x, slot_ids, a_stack, b_stack, scales)
 
 
+# ---------------------------------------------------------------- MXFP4
+
+MXFP4_SCALE_MIN = 8    # scale bytes outside [8, 247] could dequantise to a
+MXFP4_SCALE_MAX = 247  # subnormal, an infinity or NaN (0xFF): not accepted
+
+
+def validate_mxfp4_scales(w_scale: torch.Tensor) -> None:
+    """Raise ValueError if an e8m0 scale byte lies outside [8, 247]. Reads
+    the tensor on the host (synchronises on a GPU tensor): call it when
+    weights are converted or loaded, never per forward. The compute ops do
+    not scan scale bytes; feeding them a byte this rejects is outside
+    their contract."""
+    if w_scale.dtype != torch.uint8:
+        raise ValueError(
+            f"mxfp4: weight_scale must be uint8, got {w_scale.dtype}")
+    if w_scale.numel() == 0:
+        return
+    lo, hi = int(w_scale.min()), int(w_scale.max())
+    if lo < MXFP4_SCALE_MIN or hi > MXFP4_SCALE_MAX:
+        raise ValueError(
+            f"mxfp4: scale bytes span [{lo}, {hi}], outside the supported "
+            f"[{MXFP4_SCALE_MIN}, {MXFP4_SCALE_MAX}]")
+
+
+def _check_mxfp4_weight(op: str, w_packed, w_scale):
+    if w_packed.dtype != torch.uint8 or w_scale.dtype != torch.uint8:
+        raise ValueError(
+            f"{op}: weight_packed and weight_scale must be uint8, got "
+            f"{w_packed.dtype} and {w_scale.dtype}")
+    if w_packed.dim() != 2 or w_scale.dim() != 2:
+        raise ValueError(f"{op}: weight_packed and weight_scale must be 2-D")
+    N, K = w_packed.shape[0], w_packed.shape[1] * 2
+    if K < 128 or K % 128 != 0 or N < 16 or N % 16 != 0:
+        raise ValueError(
+            f"{op}: unsupported shape N={N} K={K} "
+            "(need K % 128 == 0 and N % 16 == 0)")
+    if tuple(w_scale.shape) != (N, K // 32):
+        raise ValueError(
+            f"{op}: weight_scale must be [N, K/32] = {(N, K // 32)}, got "
+            f"{tuple(w_scale.shape)}")
+    if w_scale.device != w_packed.device:
+        raise ValueError(f"{op}: weight tensors must share one device")
+    if not (w_packed.is_contiguous() and w_scale.is_contiguous()):
+        raise ValueError(f"{op}: weight tensors must be contiguous")
+    return N, K
+
+
+def _check_mxfp4_out(op: str, out, shape, device):
+    if (out.dtype != torch.bfloat16 or tuple(out.shape) != shape
+            or out.device != device or not out.is_contiguous()):
+        raise ValueError(
+            f"{op}: out must be a contiguous bf16 {shape} tensor on {device}")
+
+
+def mxfp4_linear(x, w_packed, w_scale, bias=None, out=None):
+    """W4A16 linear on MXFP4 weights:
+
+        out[m, n] = bf16( sum_k x[m, k] * dq(W)[n, k] (+ bias[n]) )
+
+    with fp32 accumulation and one rounding. x [M, K] bf16 contiguous,
+    w_packed [N, K/2] uint8, w_scale [N, K/32] uint8 (bytes in [8, 247],
+    see validate_mxfp4_scales), bias [N] bf16 or None. K % 128 == 0,
+    N % 16 == 0, any M >= 0. Static grid, no host sync, no workspace:
+    hipGraph-capturable. A row's bits depend only on that x row and the
+    weights (deterministic, batch-invariant). Unsupported input raises
+    ValueError (no silent fallback)."""
+    N, K = _check_mxfp4_weight("mxfp4_linear", w_packed, w_scale)
+    if x.dtype != torch.bfloat16:
+        raise ValueError(f"mxfp4_linear: x must be bf16, got {x.dtype}")
+    if x.dim() != 2 or x.shape[1] != K:
+        raise ValueError(
+            f"mxfp4_linear: x must be [M, {K}], got {tuple(x.shape)}")
+    if not x.is_contiguous():
+        raise ValueError("mxfp4_linear: x must be contiguous")
+    if x.device != w_packed.device:
+        raise ValueError("mxfp4_linear: x and the weights must share one device")
+    if bias is not None and (
+            bias.dtype != torch.bfloat16 or tuple(bias.shape) != (N,)
+            or bias.device != x.device or not bias.is_contiguous()):
+        raise ValueError(
+            f"mxfp4_linear: bias must be a contiguous bf16 [{N}] tensor on "
+            f"{x.device}")
+    M = x.shape[0]
+    if out is not None:
+        _check_mxfp4_out("mxfp4_linear", out, (M, N), x.device)
+    if x.is_cuda:
+        _require_native()
+        if out is None:
+            out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+        if M > 0:
+            _C.mxfp4_linear(out, x, w_packed, w_scale, bias)
+        return out
+    res = ref.mxfp4_linear(x, w_packed, w_scale, bias)
+    if out is None:
+        return res
+    out.copy_(res)
+    return out
+
+
+def mxfp4_dequant(w_packed, w_scale, out=None):
+    """Expand MXFP4 weights to bf16 [N, K] (exact; code 8 reads +0.0).
+    Same weight contract as mxfp4_linear."""
+    N, K = _check_mxfp4_weight("mxfp4_dequant", w_packed, w_scale)
+    if out is not None:
+        _check_mxfp4_out("mxfp4_dequant", out, (N, K), w_packed.device)
+    if w_packed.is_cuda:
+        _require_native()
+        if out is None:
+            out = torch.empty((N, K), dtype=torch.bfloat16,
+                              device=w_packed.device)
+        _C.mxfp4_dequant(out, w_packed, w_scale)
+        return out
+    res = ref.mxfp4_dequant(w_packed, w_scale)
+    if out is None:
+        return res
+    out.copy_(res)
+    return out
+
+
 # ---------------------------------------------------------------- sampling
 
 def sample_tokens(logits, temperature, top_k, top_p, min_p, rng):

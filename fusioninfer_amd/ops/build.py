@@ -32,6 +32,7 @@ SOURCES = [
     "penalties.hip",
     "spec_verify.hip",
     "logit_mods.hip",
+    "mxfp4_gemm.hip",
 ]
 
 

@@ -53,6 +53,11 @@ void launch_moe_combine(u16*, const u16*, const int*, const float*, int, int,
 void launch_lora_apply(u16*, u16*, const u16*, const int*, const u16*,
                        const u16*, const float*, int, int, int, int, int,
                        hipStream_t);
+void launch_mxfp4_linear(u16*, const u16*, const unsigned char*,
+                         const unsigned char*, const u16*, int, int, int,
+                         hipStream_t);
+void launch_mxfp4_dequant(u16*, const unsigned char*, const unsigned char*,
+                          int64_t, hipStream_t);
 void launch_sample_tokens(int64_t*, const float*, const float*, const int*,
                           const float*, const float*, const int64_t*, int,
                           int, hipStream_t);
@@ -604,6 +609,84 @@ void lora_apply(at::Tensor out, at::Tensor y_ws, at::Tensor x,
                         static_cast<int>(S), current_stream());
 }
 
+// shared checks of the MXFP4 ops: weight_packed [N, K/2] uint8 and
+// weight_scale [N, K/32] uint8, both contiguous on the GPU
+void check_mxfp4_weight(const at::Tensor& w_packed, const at::Tensor& w_scale,
+                        int64_t* N, int64_t* K) {
+  TORCH_CHECK(w_packed.is_cuda() && w_scale.is_cuda(),
+              "mxfp4: weights must be on GPU");
+  TORCH_CHECK(w_packed.scalar_type() == at::kByte &&
+                  w_scale.scalar_type() == at::kByte,
+              "mxfp4: weight_packed and weight_scale must be uint8");
+  TORCH_CHECK(w_packed.dim() == 2 && w_scale.dim() == 2 &&
+                  w_packed.is_contiguous() && w_scale.is_contiguous(),
+              "mxfp4: weights must be 2-D and contiguous");
+  *N = w_packed.size(0);
+  *K = w_packed.size(1) * 2;
+  TORCH_CHECK(*N >= 16 && *N % 16 == 0 && *K >= 128 && *K % 128 == 0 &&
+                  *N < (1LL << 31) && *K < (1LL << 31),
+              "mxfp4: need K % 128 == 0 and N % 16 == 0");
+  TORCH_CHECK(w_scale.size(0) == *N && w_scale.size(1) == *K / 32,
+              "mxfp4: weight_scale must be [N, K/32]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(w_packed.data_ptr()) % 16 == 0,
+              "mxfp4: weight_packed must be 16-byte aligned");
+}
+
+void mxfp4_linear(at::Tensor out, at::Tensor x, at::Tensor w_packed,
+                  at::Tensor w_scale, c10::optional<at::Tensor> bias) {
+  CHECK_BF16_CUDA(out);
+  CHECK_BF16_CUDA(x);
+  int64_t N, K;
+  check_mxfp4_weight(w_packed, w_scale, &N, &K);
+  TORCH_CHECK(x.dim() == 2 && out.dim() == 2 && x.is_contiguous() &&
+                  out.is_contiguous(),
+              "mxfp4_linear: x and out must be 2-D and contiguous");
+  const int64_t M = x.size(0);
+  TORCH_CHECK(M >= 1 && M <= 65535 * 16 && x.size(1) == K &&
+                  out.size(0) == M && out.size(1) == N,
+              "mxfp4_linear: need x [M, K], out [M, N], 1 <= M <= 1048560");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "mxfp4_linear: x must be 16-byte aligned");
+  TORCH_CHECK(x.get_device() == out.get_device() &&
+                  x.get_device() == w_packed.get_device() &&
+                  x.get_device() == w_scale.get_device(),
+              "mxfp4_linear: tensors must share one device");
+  const u16* bias_p = nullptr;
+  if (bias.has_value()) {
+    CHECK_BF16_CUDA(*bias);
+    TORCH_CHECK(bias->dim() == 1 && bias->numel() == N &&
+                    bias->is_contiguous() &&
+                    bias->get_device() == x.get_device(),
+                "mxfp4_linear: bias must be a contiguous [N] bf16 tensor");
+    bias_p = bf16_cptr(*bias);
+  }
+  fi::launch_mxfp4_linear(
+      bf16_ptr(out), bf16_cptr(x),
+      static_cast<const unsigned char*>(w_packed.data_ptr()),
+      static_cast<const unsigned char*>(w_scale.data_ptr()), bias_p,
+      static_cast<int>(M), static_cast<int>(N), static_cast<int>(K),
+      current_stream());
+}
+
+void mxfp4_dequant(at::Tensor out, at::Tensor w_packed, at::Tensor w_scale) {
+  CHECK_BF16_CUDA(out);
+  int64_t N, K;
+  check_mxfp4_weight(w_packed, w_scale, &N, &K);
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == N && out.size(1) == K &&
+                  out.is_contiguous() &&
+                  out.get_device() == w_packed.get_device() &&
+                  out.get_device() == w_scale.get_device(),
+              "mxfp4_dequant: out must be a contiguous [N, K] bf16 tensor");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(out.data_ptr()) % 16 == 0,
+              "mxfp4_dequant: out must be 16-byte aligned");
+  const int64_t nblocks = N * (K / 32);
+  TORCH_CHECK(nblocks / 256 < (1LL << 31) - 1, "mxfp4_dequant: too large");
+  fi::launch_mxfp4_dequant(
+      bf16_ptr(out), static_cast<const unsigned char*>(w_packed.data_ptr()),
+      static_cast<const unsigned char*>(w_scale.data_ptr()), nblocks,
+      current_stream());
+}
+
 void sample_tokens(at::Tensor out, at::Tensor logits, at::Tensor temperature,
                    at::Tensor top_k, at::Tensor top_p, at::Tensor min_p,
                    at::Tensor rng) {
@@ -911,6 +994,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "(vLLM moe_align_block_size analog)");
   m.def("moe_router_topk", &moe_router_topk,
         "fused router tail: softmax + top-k + optional renormalize");
+  m.def("mxfp4_linear", &mxfp4_linear,
+        "W4A16 linear on MXFP4 weights (bf16 in/out, fp32 accumulation)");
+  m.def("mxfp4_dequant", &mxfp4_dequant, "expand MXFP4 weights to bf16");
   m.def("lora_apply", &lora_apply,
         "batched multi-LoRA shrink + expand indexed by per-token slot ids "
         "(in-place on out)");

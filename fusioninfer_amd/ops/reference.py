@@ -702,3 +702,33 @@ def spec_accept(sampled, drafts, span_cu, emitted, n_emit):
                     break
         n_emit[s] = n
     return emitted, n_emit
+
+
+# ------------------------------------------------------------------ MXFP4
+
+# e2m1 code -> value; bit 3 is the sign, code 8 (negative zero) reads +0.0
+MXFP4_TABLE = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0,
+               0.0, -0.5, -1.0, -1.5, -2.0, -3.0, -4.0, -6.0)
+
+
+def mxfp4_dequant(w_packed: torch.Tensor, w_scale: torch.Tensor) -> torch.Tensor:
+    """OCP MXFP4 -> bf16 [N, K], exact. w_packed [N, K/2] uint8 holds k = 2j
+    in the low nibble of byte j and k = 2j + 1 in the high nibble; w_scale
+    [N, K/32] uint8 is the e8m0 scale 2^(s - 127) of each 32-k block, with
+    s in [8, 247] so every product is zero or a normal bf16."""
+    N, half = w_packed.shape
+    lut = torch.tensor(MXFP4_TABLE, dtype=torch.float32, device=w_packed.device)
+    codes = torch.stack((w_packed & 0xF, w_packed >> 4), dim=-1).reshape(N, -1)
+    vals = lut[codes.long()]
+    # 2^(s - 127) from its bit pattern: exact for every s in [1, 254]
+    scale = (w_scale.to(torch.int32) << 23).view(torch.float32)
+    out = vals.view(N, -1, 32) * scale.unsqueeze(-1)
+    return out.view(N, 2 * half).to(torch.bfloat16)
+
+
+def mxfp4_linear(x, w_packed, w_scale, bias=None) -> torch.Tensor:
+    """x [M, K] bf16 @ dq(W)^T (+ bias) in fp32, rounded to bf16 once."""
+    out = x.float() @ mxfp4_dequant(w_packed, w_scale).float().t()
+    if bias is not None:
+        out = out + bias.float()
+    return out.to(torch.bfloat16)

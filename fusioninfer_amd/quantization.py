@@ -1,4 +1,4 @@
-"""FP8 (OCP e4m3) quantized linear path.
+"""Quantized linear paths: FP8 (OCP e4m3, W8A8) and MXFP4 (W4A16, below).
 
 gfx950 runs OCP fp8 MFMA at ~2x the bf16 rate and halves weight-read
 bytes — decode-time GEMMs are weight-bandwidth-bound, so fp8 weights pay
@@ -14,8 +14,11 @@ Note: gfx950 fp8 is OCP e4m3fn — NOT the MI300X fnuz variant
 
 from __future__ import annotations
 
+import os
+
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from fusioninfer_amd.distributed import parallel_state as ps
 
@@ -87,6 +90,157 @@ def convert_linear_to_fp8(module: nn.Module) -> int:
             m.forward = _make_fp8_forward(m)
             converted += 1
     return converted
+
+
+# ------------------------------------------------------------------ MXFP4
+#
+# Weight-only 4-bit mode (`--quantization mxfp4`): projection weights are
+# stored as OCP Microscaling MXFP4 along K — e2m1 elements (1 sign, 2
+# exponent, 1 mantissa bit; magnitudes {0, 0.5, 1, 1.5, 2, 3, 4, 6}), two per
+# byte with k even in the low nibble, and one e8m0 scale byte 2^(s - 127) per
+# 32 consecutive k of an output row: 4.25 bits per weight. Activations stay
+# bf16. Scale bytes are confined to [8, 247] — the quantiser clamps to it and
+# validate_mxfp4_scales rejects anything else, 0xFF (NaN) included — so every
+# dequantised value is zero or a normal bf16 and dequantisation is exact: the
+# W4A16 GEMM is "a bf16 GEMM with fp32 accumulation on dequant(W)".
+
+MXFP4_BLOCK = 32
+# Largest M served by the weight-streaming HIP GEMM (ops.mxfp4_linear);
+# larger batches expand the weight into the shared bf16 scratch and call the
+# library GEMM. The streaming kernel re-reads x once per column tile, so it
+# loses once x traffic outweighs the 4x smaller weight read. Measured on
+# the Qwen3-8B shapes (profiles/r12_mxfp4.md): it beats dequant + F.linear
+# on all four up to M = 32; at M = 64 it loses on down_proj (K = 12288).
+MXFP4_MAX_M = int(os.environ.get("FI_MXFP4_MAX_M", "32"))
+
+
+def validate_mxfp4_scales(weight_scale: torch.Tensor) -> None:
+    """Raise ValueError on an e8m0 scale byte outside [8, 247]. Host-side
+    (synchronises on a GPU tensor); runs at conversion or load time only."""
+    from fusioninfer_amd import ops
+
+    ops.validate_mxfp4_scales(weight_scale)
+
+
+def quantize_weight_mxfp4(w: torch.Tensor):
+    """[N, K] -> (packed [N, K/2] uint8, scale [N, K/32] uint8). Per 32-k
+    block: amax in fp32; s = 127 for an all-zero block, else
+    clamp(floor(log2(amax)) - 2 + 127, 8, 247) (2 = e2m1's emax, as in the
+    OCP spec); elements are w / 2^(s - 127) rounded to the nearest grid
+    point, ties to the code with even mantissa bit, saturating at +-6.
+    Zeros are stored as code 0, never as negative zero."""
+    if w.dim() != 2 or w.shape[1] % MXFP4_BLOCK != 0:
+        raise ValueError(
+            f"quantize_weight_mxfp4: need [N, K] with K % 32 == 0, got "
+            f"{tuple(w.shape)}")
+    wf = w.float()
+    if not bool(torch.isfinite(wf).all()):
+        raise ValueError("quantize_weight_mxfp4: non-finite weight")
+    N, K = wf.shape
+    blocks = wf.view(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    amax = blocks.abs().amax(dim=-1)
+    # amax = m * 2^e with m in [0.5, 1): floor(log2(amax)) = e - 1, exactly
+    _, e = torch.frexp(amax)
+    s = (e.to(torch.int32) - 1 - 2 + 127).clamp(8, 247)
+    s = torch.where(amax == 0, torch.full_like(s, 127), s)
+    # 2^(127 - s) from its bit pattern: the scaling below is exact
+    inv = ((254 - s) << 23).view(torch.float32)
+    a = (blocks * inv.unsqueeze(-1)).abs()
+    # midpoints of the grid; a tie goes to the neighbour with mantissa bit 0
+    code = ((a > 0.25).to(torch.uint8) + (a >= 0.75).to(torch.uint8)
+            + (a > 1.25).to(torch.uint8) + (a >= 1.75).to(torch.uint8)
+            + (a > 2.5).to(torch.uint8) + (a >= 3.5).to(torch.uint8)
+            + (a > 5.0).to(torch.uint8))
+    code = code | (((blocks < 0) & (code > 0)).to(torch.uint8) << 3)
+    code = code.view(N, K // 2, 2)
+    packed = code[..., 0] | (code[..., 1] << 4)
+    return packed.contiguous(), s.to(torch.uint8).contiguous()
+
+
+def dequantize_mxfp4(packed: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """Exact inverse map of the format: bf16 [N, K]."""
+    from fusioninfer_amd.ops import reference
+
+    return reference.mxfp4_dequant(packed, scale)
+
+
+class _Mxfp4Scratch:
+    """One bf16 buffer shared by every converted layer of a model, sized to
+    the largest of them, for the large-M path (dequant, then library GEMM).
+    Allocated once at conversion, so its address is stable for captured
+    graphs and the KV-cache sizing sees it. Sharing it assumes all model
+    forwards run on one stream: a layer's GEMM must finish reading the
+    buffer before the next layer's dequant overwrites it, which stream
+    order gives and concurrent streams would not."""
+
+    def __init__(self):
+        self.buf = None
+
+    def reserve(self, numel: int, device) -> None:
+        self.buf = torch.empty(numel, dtype=torch.bfloat16, device=device)
+
+    def view(self, n: int, k: int) -> torch.Tensor:
+        return self.buf[: n * k].view(n, k)
+
+
+def convert_linear_to_mxfp4(module: nn.Module) -> int:
+    """Convert every projection Linear in a CausalLM to MXFP4 storage:
+    `weight` is replaced by the buffers `weight_packed` [N, K/2] and
+    `weight_scale` [N, K/32] and the bf16 tensor is freed. Returns the
+    number of converted layers. lm_head/embedding stay bf16."""
+    from fusioninfer_amd.distributed.layers import (
+        MergedColumnParallelLinear,
+        RowParallelLinear,
+    )
+
+    layers = [
+        m for m in module.modules()
+        if isinstance(m, (MergedColumnParallelLinear, RowParallelLinear))
+    ]
+    for m in layers:  # reject before anything is converted
+        N, K = m.weight.shape
+        if K % 128 != 0 or N % 16 != 0:
+            what = ("in_per_rank" if isinstance(m, RowParallelLinear)
+                    else "in_features")
+            raise ValueError(
+                f"mxfp4: {type(m).__name__} shard [{N}, {K}] is unsupported: "
+                f"{what} must be a multiple of 128 and the output rows a "
+                "multiple of 16")
+    scratch = _Mxfp4Scratch()
+    if layers and layers[0].weight.is_cuda:
+        scratch.reserve(max(m.weight.numel() for m in layers),
+                        layers[0].weight.device)
+    for m in layers:
+        w = m.weight.data
+        packed, scale = quantize_weight_mxfp4(w)
+        validate_mxfp4_scales(scale)
+        del m.weight
+        m.register_buffer("weight_packed", packed, persistent=False)
+        m.register_buffer("weight_scale", scale, persistent=False)
+        m.forward = _make_mxfp4_forward(m, scratch)
+    return len(layers)
+
+
+def _make_mxfp4_forward(m, scratch):
+    from fusioninfer_amd import ops
+
+    is_row_parallel = hasattr(m, "in_per_rank")
+    bias = getattr(m, "bias", None)
+    N, K = m.weight_packed.shape[0], m.weight_packed.shape[1] * 2
+
+    def fwd(x):
+        x = x.contiguous()
+        if x.is_cuda and x.shape[0] > MXFP4_MAX_M:
+            w = ops.mxfp4_dequant(m.weight_packed, m.weight_scale,
+                                  out=scratch.view(N, K))
+            out = F.linear(x, w, bias)
+        else:
+            out = ops.mxfp4_linear(x, m.weight_packed, m.weight_scale, bias)
+        if is_row_parallel:
+            out = ps.tp_all_reduce(out)
+        return out
+
+    return fwd
 
 
 def _make_fp8_forward(m):

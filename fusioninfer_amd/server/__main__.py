@@ -37,7 +37,8 @@ def parse_args(argv=None):
                    help='JSON: {"kv_connector": "RcclConnector", '
                         '"kv_role": "kv_producer"|"kv_consumer"}')
     p.add_argument("--enforce-eager", action="store_true")
-    p.add_argument("--quantization", choices=["fp8"], default=None)
+    p.add_argument("--quantization", choices=["fp8", "mxfp4"],
+                   default=None)
     p.add_argument("--sampler-backend", choices=["torch", "fused"],
                    default="torch",
                    help="fused: one HIP sampling launch per step "

@@ -1022,6 +1022,57 @@ class _OneTarget:
         self.layers = [{"t": (a, b, scales)}]
 
 
+def bench_mxfp4():
+    """The four Qwen3-8B projections at decode-to-prefill batch sizes:
+    mxfp4_linear, mxfp4_dequant + F.linear, bf16 F.linear and the fp8
+    _scaled_mm path. Median device-event time per call; GB/s is the
+    weight bytes each path has to stream (4.25 / 16 / 8 bits per weight;
+    dequant + F.linear also writes and re-reads the bf16 copy) over that
+    time."""
+    import torch.nn.functional as F
+
+    from fusioninfer_amd import ops
+    from fusioninfer_amd.quantization import (
+        fp8_linear, quantize_weight_fp8, quantize_weight_mxfp4)
+
+    shapes = [("qkv", 6144, 4096), ("o", 4096, 4096),
+              ("gate_up", 24576, 4096), ("down", 4096, 12288)]
+    print("\n## MXFP4 W4A16 projections (Qwen3-8B shapes, median us, "
+          "weight GB/s)")
+    print("| layer NxK | M | mxfp4_linear | dequant+linear | bf16 linear | "
+          "fp8 scaled_mm | bf16/mxfp4 |")
+    print("|---|---|---|---|---|---|---|")
+    for name, N, K in shapes:
+        w = torch.randn(N, K, device="cuda", dtype=torch.bfloat16) * 0.02
+        packed, scale = quantize_weight_mxfp4(w)
+        w8, s8 = quantize_weight_fp8(w)
+        scratch = torch.empty(N, K, device="cuda", dtype=torch.bfloat16)
+        b4 = N * K // 2 + N * K // 32
+        b16 = 2 * N * K
+        for M in (1, 8, 32, 64, 128, 256, 512):
+            x = torch.randn(M, K, device="cuda", dtype=torch.bfloat16)
+            out = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
+
+            def dq_linear():
+                ops.mxfp4_dequant(packed, scale, out=scratch)
+                return F.linear(x, scratch)
+
+            cols = []
+            for fn, nbytes in (
+                (lambda: ops.mxfp4_linear(x, packed, scale, out=out), b4),
+                (dq_linear, b4 + 2 * b16),
+                (lambda: F.linear(x, w), b16),
+                (lambda: fp8_linear(x, w8, s8), N * K),
+            ):
+                for _ in range(10):
+                    fn()
+                us = _median(_event_times_us(fn, 100))
+                cols.append((us, nbytes / us / 1e3))
+            print(f"| {name} {N}x{K} | {M} | "
+                  + " | ".join(f"{u:.1f} ({g:.0f})" for u, g in cols)
+                  + f" | {cols[2][0] / cols[0][0]:.2f}x |", flush=True)
+
+
 if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "all"
     torch.manual_seed(0)
@@ -1056,3 +1107,5 @@ if __name__ == "__main__":
         bench_guided_spec_e2e()
     if which in ("bias_pipelining", "all"):
         bench_bias_pipelining()
+    if which in ("mxfp4", "all"):
+        bench_mxfp4()

@@ -37,6 +37,10 @@ class ModelConfig:
     model_path: Optional[str] = None
     # None = bf16; "fp8" = OCP e4m3 weights + dynamic per-token activations
     quantization: Optional[str] = None
+    # with quantization == "mxfp4": store the MoE experts as MXFP4 too and
+    # run them on the grouped W4A16 GEMM. Off: an MoE model is refused in
+    # mxfp4 mode. No effect on a dense model.
+    mxfp4_moe_experts: bool = False
     # MoE (Qwen3-MoE family): num_experts 0 = dense MLP
     num_experts: int = 0
     num_experts_per_tok: int = 8

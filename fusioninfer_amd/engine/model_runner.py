@@ -40,9 +40,15 @@ class ModelRunner:
         self.is_cuda = self.device.type == "cuda"
         mc = cfg.model
         torch.manual_seed(cfg.seed)
-        if mc.quantization == "mxfp4" and mc.is_moe:
+        if mc.mxfp4_moe_experts and mc.quantization != "mxfp4":
+            raise ValueError(
+                "mxfp4_moe_experts needs quantization='mxfp4', got "
+                f"{mc.quantization!r}")
+        if (mc.quantization == "mxfp4" and mc.is_moe
+                and not mc.mxfp4_moe_experts):
             # the experts are ~90 % of an MoE model's weights and would
-            # stay bf16: refuse rather than mislead
+            # stay bf16: refuse rather than mislead (mxfp4_moe_experts
+            # converts them too; opt-in)
             raise ValueError("mxfp4 does not cover MoE experts yet")
         fp8_ckpt = False
         if mc.model_path:
@@ -86,6 +92,14 @@ class ModelRunner:
 
                 n = convert_linear_to_mxfp4(self.model)
                 assert n > 0
+                if mc.is_moe:
+                    from fusioninfer_amd.quantization import (
+                        convert_moe_experts_to_mxfp4,
+                    )
+
+                    # drops the experts' bf16 weights and MFMA pack before
+                    # the KV cache is sized
+                    assert convert_moe_experts_to_mxfp4(self.model) > 0
         if mc.quantization not in (None, "fp8", "mxfp4"):
             raise ValueError(f"unknown quantization {mc.quantization!r}")
         if self.is_cuda and os.environ.get(

@@ -216,6 +216,9 @@ class MoEMLP(nn.Module):
         self.e_start = ps.tp_rank() * (E // tp)
         self.e_end = self.e_start + E // tp
         self.fp8 = cfg.quantization == "fp8"
+        # set by quantization.convert_moe_experts_to_mxfp4: experts live in
+        # gate_up_packed / gate_up_scale / down_packed / down_scale only
+        self.mxfp4 = False
         H, inter = cfg.hidden_size, cfg.moe_intermediate_size
         base = torch.initial_seed() % (2**62)
         dev = torch.empty(0).device  # honor the ambient torch.device context
@@ -355,12 +358,20 @@ class MoEMLP(nn.Module):
             out.index_add_(0, rows, y.float() * flat_w[sel].unsqueeze(1))
         return ps.tp_all_reduce(out.to(torch.bfloat16))
 
+    def _refuse_after_mxfp4(self, what: str):
+        if self.mxfp4:
+            raise RuntimeError(
+                f"MoEMLP.{what}: the experts of layer {self.layer_idx} were "
+                "converted to MXFP4 and their bf16 weights dropped; expert "
+                "weights cannot be rewritten after 4-bit conversion")
+
     def invalidate_packed(self):
         """Drop the packed-weight cache (the weight loader calls this:
         mutations through Parameter.data don't bump tensor._version).
         Frees the stale packed copy immediately so the repack never
         doubles up, then repacks eagerly on GPU (keeps the footprint
         visible before any KV-cache sizing)."""
+        self._refuse_after_mxfp4("invalidate_packed")
         stored = self.gate_up_fp8 if self.fp8 else self.gate_up_t
         if stored.numel() == 0 and self.e_end > self.e_start:
             raise RuntimeError(
@@ -383,8 +394,9 @@ class MoEMLP(nn.Module):
         re-materializes exact contents from the packed cache if the
         loader needs to write again. The runner calls this after weight
         load and BEFORE KV-cache sizing, so the freed bytes become KV
-        blocks. CPU keeps the unpacked form (it IS the compute path)."""
-        if self.e_end == self.e_start:
+        blocks. CPU keeps the unpacked form (it IS the compute path).
+        A no-op after MXFP4 conversion: nothing bf16 is left to release."""
+        if self.mxfp4 or self.e_end == self.e_start:
             return
         if self.fp8:
             if not self.gate_up_fp8.is_cuda or self.gate_up_fp8.numel() == 0:
@@ -412,6 +424,7 @@ class MoEMLP(nn.Module):
         params EXACTLY from the packed cache (unpack_moe_weights is pure
         view/permute tensor ops, so it runs on-device). No-op when the
         unpacked form is already resident."""
+        self._refuse_after_mxfp4("ensure_unpacked")
         if self.e_end == self.e_start:
             return
         from fusioninfer_amd.ops.reference import unpack_moe_weights
@@ -592,7 +605,39 @@ class MoEMLP(nn.Module):
         ops.moe_combine(out, y, pos, topv.reshape(-1).float().contiguous())
         return ps.tp_all_reduce(out)
 
+    def _forward_mxfp4_grouped(self, x: torch.Tensor) -> torch.Tensor:
+        """MXFP4 experts (W4A16): the shape of _forward_grouped with the
+        grouped GEMMs reading packed 4-bit weights. No host sync on the
+        GPU, so MoE decode graphs capture it unchanged; on the CPU the same
+        composition runs through the reference ops."""
+        T, H = x.shape
+        E_local = self.e_end - self.e_start
+        logits = x.float() @ self.router_weight.float().T
+        topv, topi = self._router_topk(logits)
+        # this kernel's crossover is higher than the bf16 one's: measured on
+        # the Qwen3-30B-A3B shapes, block_m 16 still wins at 128 rows per
+        # local expert and block_m 128 from 256 on
+        # (profiles/r13_mxfp4_moe.md)
+        block_m = 128 if T * self.top_k >= 256 * E_local else 16
+        sorted_ids, expert_ids, n_valid, pos, PM = self._moe_align(
+            topi, block_m
+        )
+        inter = self.down_packed.shape[2] * 2
+        act = torch.empty(PM, inter, dtype=x.dtype, device=x.device)
+        ops.moe_gemm_mxfp4(act, x, self.gate_up_packed, self.gate_up_scale,
+                           sorted_ids, expert_ids, n_valid, block_m,
+                           gate_up=True)
+        y = torch.empty(PM, H, dtype=x.dtype, device=x.device)
+        ops.moe_gemm_mxfp4(y, act, self.down_packed, self.down_scale,
+                           sorted_ids, expert_ids, n_valid, block_m,
+                           gate_up=False)
+        out = torch.empty(T, H, dtype=x.dtype, device=x.device)
+        ops.moe_combine(out, y, pos, topv.reshape(-1).float().contiguous())
+        return ps.tp_all_reduce(out)
+
     def forward(self, x: torch.Tensor, lora=None) -> torch.Tensor:
+        if self.mxfp4:
+            return self._forward_mxfp4_grouped(x.contiguous())
         if self.fp8:
             return self._forward_fp8(x)
         if x.is_cuda:

@@ -714,6 +714,84 @@ def mxfp4_dequant(w_packed, w_scale, out=None):
     return out
 
 
+def moe_gemm_mxfp4(out, a, w_packed, w_scale, sorted_ids, expert_ids, n_valid,
+                   block_m: int, gate_up: bool):
+    """Grouped W4A16 GEMM over block-aligned expert segments (the moe_gemm
+    contract) with MXFP4 expert weights and bf16 activations.
+
+    out [PM, N] bf16; a = x [T, K] (gate_up, rows gathered via sorted_ids)
+    or act [PM, K]; w_packed [E, NB, K/2] and w_scale [E, NB, K/32] uint8
+    hold each expert in the row format of mxfp4_linear (scale bytes in
+    [8, 247], see validate_mxfp4_scales), NB = 2N when gate_up (gate rows,
+    then up rows), else N. K % 128 == 0, N % 16 == 0, block_m 16 or 128.
+    n_valid: device int32 scalar with the real m-tile count; tiles at or
+    past it are not touched. gate_up=True fuses silu(gate) * up. Static
+    grid, no host sync, no workspace: hipGraph-capturable. A row's bits
+    depend only on its A row and its expert's weights, not on block_m, its
+    slot or the rest of the batch. Unsupported input raises ValueError
+    before any launch (no silent fallback)."""
+    op = "moe_gemm_mxfp4"
+    if block_m not in (16, 128):
+        raise ValueError(f"{op}: block_m must be 16 or 128, got {block_m}")
+    if out.dtype != torch.bfloat16 or a.dtype != torch.bfloat16:
+        raise ValueError(
+            f"{op}: out and a must be bf16, got {out.dtype} and {a.dtype}")
+    if w_packed.dtype != torch.uint8 or w_scale.dtype != torch.uint8:
+        raise ValueError(
+            f"{op}: w_packed and w_scale must be uint8, got "
+            f"{w_packed.dtype} and {w_scale.dtype}")
+    if (sorted_ids.dtype != torch.int32 or expert_ids.dtype != torch.int32
+            or n_valid.dtype != torch.int32):
+        raise ValueError(
+            f"{op}: sorted_ids, expert_ids and n_valid must be int32")
+    if out.dim() != 2 or a.dim() != 2 or w_packed.dim() != 3 \
+            or w_scale.dim() != 3 or sorted_ids.dim() != 1 \
+            or expert_ids.dim() != 1 or n_valid.numel() != 1:
+        raise ValueError(
+            f"{op}: need out [PM, N], a [rows, K], w_packed [E, NB, K/2], "
+            "w_scale [E, NB, K/32], sorted_ids [PM], expert_ids [PM/block_m] "
+            "and a one-element n_valid")
+    tensors = (out, a, w_packed, w_scale, sorted_ids, expert_ids, n_valid)
+    if any(t.device != out.device for t in tensors):
+        raise ValueError(f"{op}: all tensors must share one device")
+    if not all(t.is_contiguous() for t in tensors):
+        raise ValueError(f"{op}: all tensors must be contiguous")
+    PM, N = out.shape
+    K = a.shape[1]
+    NB = 2 * N if gate_up else N
+    if K < 128 or K % 128 != 0 or N < 16 or N % 16 != 0:
+        raise ValueError(
+            f"{op}: unsupported shape N={N} K={K} "
+            "(need K % 128 == 0 and N % 16 == 0)")
+    E = w_packed.shape[0]
+    if E < 1 or tuple(w_packed.shape) != (E, NB, K // 2) \
+            or tuple(w_scale.shape) != (E, NB, K // 32):
+        raise ValueError(
+            f"{op}: need w_packed [E, {NB}, {K // 2}] and w_scale "
+            f"[E, {NB}, {K // 32}], got {tuple(w_packed.shape)} and "
+            f"{tuple(w_scale.shape)}")
+    if sorted_ids.numel() % block_m != 0 or sorted_ids.numel() != PM \
+            or PM < block_m:
+        raise ValueError(
+            f"{op}: sorted_ids must hold PM = {PM} slots, a positive "
+            f"multiple of block_m = {block_m}; got {sorted_ids.numel()}")
+    if expert_ids.numel() < PM // block_m:
+        raise ValueError(
+            f"{op}: expert_ids must cover {PM // block_m} m-tiles, got "
+            f"{expert_ids.numel()}")
+    if a.shape[0] < 1 or (not gate_up and a.shape[0] != PM):
+        raise ValueError(
+            f"{op}: a must be [{PM}, {K}] without gate_up and have at least "
+            f"one row with it, got {tuple(a.shape)}")
+    if out.is_cuda:
+        _require_native()
+        _C.moe_gemm_mxfp4(out, a, w_packed, w_scale, sorted_ids, expert_ids,
+                          n_valid, block_m, gate_up)
+        return out
+    return ref.moe_gemm_mxfp4(out, a, w_packed, w_scale, sorted_ids,
+                              expert_ids, n_valid, block_m, gate_up)
+
+
 # ---------------------------------------------------------------- sampling
 
 def sample_tokens(logits, temperature, top_k, top_p, min_p, rng):

@@ -33,6 +33,7 @@ SOURCES = [
     "spec_verify.hip",
     "logit_mods.hip",
     "mxfp4_gemm.hip",
+    "moe_mxfp4_gemm.hip",
 ]
 
 

@@ -58,6 +58,9 @@ void launch_mxfp4_linear(u16*, const u16*, const unsigned char*,
                          hipStream_t);
 void launch_mxfp4_dequant(u16*, const unsigned char*, const unsigned char*,
                           int64_t, hipStream_t);
+void launch_moe_gemm_mxfp4(u16*, const u16*, const unsigned char*,
+                           const unsigned char*, const int*, const int*,
+                           const int*, int, int, int, int, bool, hipStream_t);
 void launch_sample_tokens(int64_t*, const float*, const float*, const int*,
                           const float*, const float*, const int64_t*, int,
                           int, hipStream_t);
@@ -687,6 +690,72 @@ void mxfp4_dequant(at::Tensor out, at::Tensor w_packed, at::Tensor w_scale) {
       current_stream());
 }
 
+// grouped W4A16 GEMM: w_packed [E, NB, K/2], w_scale [E, NB, K/32] uint8,
+// NB = 2N when gate_up; a = x [T, K] (gate_up) or act [PM, K]
+void moe_gemm_mxfp4(at::Tensor out, at::Tensor a, at::Tensor w_packed,
+                    at::Tensor w_scale, at::Tensor sorted_ids,
+                    at::Tensor expert_ids, at::Tensor n_valid,
+                    int64_t block_m, bool gate_up) {
+  CHECK_BF16_CUDA(out);
+  CHECK_BF16_CUDA(a);
+  TORCH_CHECK(out.dim() == 2 && a.dim() == 2 && out.is_contiguous() &&
+                  a.is_contiguous(),
+              "moe_gemm_mxfp4: out and a must be 2-D and contiguous");
+  TORCH_CHECK(w_packed.is_cuda() && w_scale.is_cuda() &&
+                  w_packed.scalar_type() == at::kByte &&
+                  w_scale.scalar_type() == at::kByte &&
+                  w_packed.dim() == 3 && w_scale.dim() == 3 &&
+                  w_packed.is_contiguous() && w_scale.is_contiguous(),
+              "moe_gemm_mxfp4: weights must be contiguous 3-D uint8 on GPU");
+  TORCH_CHECK(sorted_ids.is_cuda() && expert_ids.is_cuda() &&
+                  n_valid.is_cuda() && sorted_ids.scalar_type() == at::kInt &&
+                  expert_ids.scalar_type() == at::kInt &&
+                  n_valid.scalar_type() == at::kInt &&
+                  sorted_ids.is_contiguous() && expert_ids.is_contiguous() &&
+                  n_valid.numel() == 1,
+              "moe_gemm_mxfp4: sorted_ids, expert_ids, n_valid must be "
+              "contiguous int32 on GPU");
+  TORCH_CHECK(block_m == 16 || block_m == 128,
+              "moe_gemm_mxfp4: block_m must be 16 or 128");
+  const int64_t K = a.size(1);
+  const int64_t N = out.size(1);
+  const int64_t PM = out.size(0);
+  const int64_t NB = gate_up ? 2 * N : N;
+  TORCH_CHECK(K >= 128 && K % 128 == 0 && N >= 16 && N % 16 == 0 &&
+                  K < (1LL << 31) && NB < (1LL << 31),
+              "moe_gemm_mxfp4: need K % 128 == 0 and N % 16 == 0");
+  TORCH_CHECK(PM >= block_m && PM % block_m == 0 && PM < (1LL << 31),
+              "moe_gemm_mxfp4: padded rows must be block_m-aligned");
+  TORCH_CHECK(w_packed.size(0) >= 1 && w_packed.size(1) == NB &&
+                  w_packed.size(2) == K / 2 &&
+                  w_scale.size(0) == w_packed.size(0) &&
+                  w_scale.size(1) == NB && w_scale.size(2) == K / 32,
+              "moe_gemm_mxfp4: need w_packed [E, NB, K/2] and w_scale "
+              "[E, NB, K/32]");
+  TORCH_CHECK(expert_ids.numel() >= PM / block_m &&
+                  sorted_ids.numel() >= PM && a.size(0) >= 1 &&
+                  (gate_up || a.size(0) >= PM),
+              "moe_gemm_mxfp4: sorted_ids / expert_ids / a too short");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(a.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(w_packed.data_ptr()) % 16 == 0,
+              "moe_gemm_mxfp4: a and w_packed must be 16-byte aligned");
+  const auto dev = out.get_device();
+  TORCH_CHECK(a.get_device() == dev && w_packed.get_device() == dev &&
+                  w_scale.get_device() == dev &&
+                  sorted_ids.get_device() == dev &&
+                  expert_ids.get_device() == dev &&
+                  n_valid.get_device() == dev,
+              "moe_gemm_mxfp4: tensors must share one device");
+  fi::launch_moe_gemm_mxfp4(
+      bf16_ptr(out), bf16_cptr(a),
+      static_cast<const unsigned char*>(w_packed.data_ptr()),
+      static_cast<const unsigned char*>(w_scale.data_ptr()),
+      sorted_ids.data_ptr<int>(), expert_ids.data_ptr<int>(),
+      n_valid.data_ptr<int>(), static_cast<int>(PM / block_m),
+      static_cast<int>(K), static_cast<int>(N), static_cast<int>(block_m),
+      gate_up, current_stream());
+}
+
 void sample_tokens(at::Tensor out, at::Tensor logits, at::Tensor temperature,
                    at::Tensor top_k, at::Tensor top_p, at::Tensor min_p,
                    at::Tensor rng) {
@@ -997,6 +1066,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mxfp4_linear", &mxfp4_linear,
         "W4A16 linear on MXFP4 weights (bf16 in/out, fp32 accumulation)");
   m.def("mxfp4_dequant", &mxfp4_dequant, "expand MXFP4 weights to bf16");
+  m.def("moe_gemm_mxfp4", &moe_gemm_mxfp4,
+        "grouped W4A16 GEMM over block-aligned expert segments with MXFP4 "
+        "expert weights (gate_up=true fuses the SwiGLU epilogue)");
   m.def("lora_apply", &lora_apply,
         "batched multi-LoRA shrink + expand indexed by per-token slot ids "
         "(in-place on out)");

@@ -732,3 +732,31 @@ def mxfp4_linear(x, w_packed, w_scale, bias=None) -> torch.Tensor:
     if bias is not None:
         out = out + bias.float()
     return out.to(torch.bfloat16)
+
+
+def moe_gemm_mxfp4(out, a, w_packed, w_scale, sorted_ids, expert_ids, n_valid,
+                   block_m: int, gate_up: bool):
+    """Grouped W4A16 GEMM on MXFP4 expert weights: the CPU path and the
+    semantic reference of the HIP kernel. w_packed [E, NB, K/2] and w_scale
+    [E, NB, K/32] hold each expert in the row format of mxfp4_linear (NB =
+    2N when gate_up: gate rows, then up rows). Only tiles below n_valid are
+    touched; sums and the SwiGLU run in fp32 and the result is rounded to
+    bf16 once."""
+    n_tiles = int(n_valid.item())
+    N = out.shape[1]
+    dq = {}
+    for mt in range(n_tiles):
+        e = int(expert_ids[mt])
+        if e not in dq:
+            dq[e] = mxfp4_dequant(w_packed[e], w_scale[e]).float()  # [NB, K]
+        rows = slice(mt * block_m, (mt + 1) * block_m)
+        if gate_up:
+            src = a[sorted_ids[rows].long()].float()
+        else:
+            src = a[rows].float()
+        acc = src @ dq[e].t()
+        if gate_up:
+            g, u = acc[:, :N], acc[:, N:]
+            acc = torch.nn.functional.silu(g) * u
+        out[rows] = acc.to(out.dtype)
+    return out

@@ -221,6 +221,60 @@ def convert_linear_to_mxfp4(module: nn.Module) -> int:
     return len(layers)
 
 
+def convert_moe_experts_to_mxfp4(module: nn.Module) -> int:
+    """Convert the experts of every MoEMLP in a CausalLM to MXFP4 storage.
+
+    Each expert is quantised on its [O, I] view (the transpose of
+    gate_up_t[e] / down_t[e]), one expert at a time, into the buffers
+    gate_up_packed [E, 2I, H/2], gate_up_scale [E, 2I, H/32], down_packed
+    [E, H, I/2] and down_scale [E, H, I/32] (gate rows first, then up rows:
+    the order of cat([gate, up])). The bf16 parameters become zero-expert
+    stand-ins that keep shape[1:], the MFMA pack cache is dropped, and
+    `mlp.mxfp4` is set: nothing bf16 of the experts stays resident. Returns
+    the number of converted layers."""
+    from fusioninfer_amd.models.model import MoEMLP
+
+    mlps = [m for m in module.modules() if isinstance(m, MoEMLP)]
+    for m in mlps:  # reject before anything is converted
+        if m.fp8 or m.mxfp4:
+            raise ValueError(
+                f"mxfp4: the experts of layer {m.layer_idx} are not bf16")
+        H, inter = m.gate_up_t.shape[1], m.down_t.shape[1]
+        if H % 128 != 0 or inter % 128 != 0:
+            raise ValueError(
+                f"mxfp4: MoE layer {m.layer_idx} experts [hidden_size={H}, "
+                f"moe_intermediate_size={inter}] are unsupported: both must "
+                "be multiples of 128")
+    for m in mlps:
+        m.ensure_unpacked()
+        E, H, inter2 = m.gate_up_t.shape
+        inter = inter2 // 2
+        dev = m.gate_up_t.device
+
+        def new(*shape):
+            return torch.empty(shape, dtype=torch.uint8, device=dev)
+
+        gu_p, gu_s = new(E, inter2, H // 2), new(E, inter2, H // 32)
+        dn_p, dn_s = new(E, H, inter // 2), new(E, H, inter // 32)
+        for e in range(E):
+            gu_p[e], gu_s[e] = quantize_weight_mxfp4(
+                m.gate_up_t.data[e].t().contiguous())
+            dn_p[e], dn_s[e] = quantize_weight_mxfp4(
+                m.down_t.data[e].t().contiguous())
+        validate_mxfp4_scales(gu_s)
+        validate_mxfp4_scales(dn_s)
+        m._pack_cache = None
+        m._pack_version = None
+        for p in (m.gate_up_t, m.down_t):
+            p.data = p.data.new_empty((0,) + tuple(p.shape[1:]))
+        m.register_buffer("gate_up_packed", gu_p, persistent=False)
+        m.register_buffer("gate_up_scale", gu_s, persistent=False)
+        m.register_buffer("down_packed", dn_p, persistent=False)
+        m.register_buffer("down_scale", dn_s, persistent=False)
+        m.mxfp4 = True
+    return len(mlps)
+
+
 def _make_mxfp4_forward(m, scratch):
     from fusioninfer_amd import ops
 

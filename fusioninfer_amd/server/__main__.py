@@ -39,6 +39,16 @@ def parse_args(argv=None):
     p.add_argument("--enforce-eager", action="store_true")
     p.add_argument("--quantization", choices=["fp8", "mxfp4"],
                    default=None)
+    p.add_argument("--mxfp4-moe-experts", action="store_true",
+                   help="with --quantization mxfp4 on an MoE model: store "
+                        "the experts as MXFP4 too (4.25 bits per weight) and "
+                        "run them on the grouped W4A16 HIP GEMM; without it "
+                        "an MoE model is refused in mxfp4 mode. Capacity "
+                        "feature: more KV blocks and a faster decode step "
+                        "than bf16 at batch 1-64 (the expert GEMMs alone "
+                        "are not faster at batch 1); prefill expert GEMMs "
+                        "(batch >= 1024 tokens) are about 2x slower "
+                        "(profiles/r13_mxfp4_moe.md)")
     p.add_argument("--sampler-backend", choices=["torch", "fused"],
                    default="torch",
                    help="fused: one HIP sampling launch per step "
@@ -125,6 +135,7 @@ def build_engine_config(args):
     mc = get_model_config(args.model)
     mc.model_path = args.model_path
     mc.quantization = args.quantization
+    mc.mxfp4_moe_experts = args.mxfp4_moe_experts
     speculative = None
     if args.speculative_config:
         from fusioninfer_amd.engine.spec_decode import SpeculativeConfig

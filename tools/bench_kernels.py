@@ -1073,6 +1073,102 @@ def bench_mxfp4():
                   + f" | {cols[2][0] / cols[0][0]:.2f}x |", flush=True)
 
 
+def bench_mxfp4_moe(rounds=3):
+    """The expert GEMM pair (gate_up with fused SwiGLU, then down) of
+    Qwen3-30B-A3B (E = 128, top-8, H = 2048, I = 768) for bf16 moe_gemm,
+    moe_gemm_fp8 and moe_gemm_mxfp4 in one process, on the same seeded
+    random routing; alignment is excluded (the fp8 pair is also given its
+    activations already quantised). Each figure is the median of 100
+    device-event times after 10 warm-up calls; `rounds` alternating rounds
+    are taken and the fastest and slowest round median printed. block_m
+    follows the bf16 / fp8 rule of MoEMLP; from T = 256 on both block_m are
+    timed to show each kernel's crossover."""
+    from fusioninfer_amd import ops
+    from fusioninfer_amd.quantization import (
+        quantize_weight_fp8, quantize_weight_mxfp4)
+
+    E, topk, H, inter = 128, 8, 2048, 768
+    dev = "cuda"
+    g = torch.Generator(device=dev).manual_seed(0)
+
+    def draw(*shape):
+        return (torch.randn(*shape, generator=g, device=dev) * 0.02).to(
+            torch.bfloat16)
+
+    w = {}
+    for name, N, K in (("gate_up", 2 * inter, H), ("down", H, inter)):
+        oi = torch.stack([draw(N, K) for _ in range(E)])  # [E, O, I]
+        q = [quantize_weight_mxfp4(oi[e]) for e in range(E)]
+        q8 = [quantize_weight_fp8(oi[e]) for e in range(E)]
+        kn = oi.transpose(1, 2).contiguous()
+        w8 = torch.stack([a for a, _ in q8]).transpose(1, 2).contiguous()
+        w[name] = dict(
+            bf16=ops.pack_moe_weights(kn),
+            fp8=ops.pack_moe_weights(w8.view(torch.int8)).view(
+                torch.float8_e4m3fn),
+            fp8_s=torch.stack([s for _, s in q8]).float().contiguous(),
+            mx_p=torch.stack([p for p, _ in q]),
+            mx_s=torch.stack([s for _, s in q]),
+        )
+        del oi, kn, w8, q, q8
+    nbytes = {"bf16": 2.0, "fp8": 1.0, "mxfp4": 4.25 / 8}
+    print("\n## MXFP4 MoE experts: gate_up + down pair, Qwen3-30B-A3B shapes "
+          f"(median us, fastest..slowest of {rounds} rounds)")
+    print("| T | block_m | bf16 moe_gemm | moe_gemm_fp8 | moe_gemm_mxfp4 | "
+          "bf16 fastest / mxfp4 slowest | fp8 fastest / mxfp4 slowest |")
+    print("|---|---|---|---|---|---|---|")
+    for T in (1, 8, 64, 256, 1024, 2048, 4096, 8192):
+        x = draw(T, H)
+        logits = torch.randn(T, E, generator=g, device=dev)
+        _, topi = ops.moe_router_topk(logits, topk, True)
+        rule = 128 if T * topk >= 64 * E else 16
+        for block_m in ((16, 128) if T >= 256 else (rule,)):
+            s, e, n, _, PM = ops.moe_align(topi, 0, E, block_m)
+            act = torch.empty(PM, inter, device=dev, dtype=torch.bfloat16)
+            y = torch.empty(PM, H, device=dev, dtype=torch.bfloat16)
+            x8, xs = ops.quant_fp8_rows(x)
+            xs = xs.float()
+            ops.moe_gemm(act, x, w["gate_up"]["bf16"], s, e, n, block_m, True)
+            a8, a_s = ops.quant_fp8_rows(act)
+            a_s = a_s.float()
+            gu, dn = w["gate_up"], w["down"]
+
+            def bf16():
+                ops.moe_gemm(act, x, gu["bf16"], s, e, n, block_m, True)
+                ops.moe_gemm(y, act, dn["bf16"], s, e, n, block_m, False)
+
+            def fp8():
+                ops.moe_gemm_fp8(act, x8, xs, gu["fp8"], gu["fp8_s"], s, e, n,
+                                 block_m, True)
+                ops.moe_gemm_fp8(y, a8, a_s, dn["fp8"], dn["fp8_s"], s, e, n,
+                                 block_m, False)
+
+            def mxfp4():
+                ops.moe_gemm_mxfp4(act, x, gu["mx_p"], gu["mx_s"], s, e, n,
+                                   block_m, True)
+                ops.moe_gemm_mxfp4(y, act, dn["mx_p"], dn["mx_s"], s, e, n,
+                                   block_m, False)
+
+            meds = {"bf16": [], "fp8": [], "mxfp4": []}
+            for _ in range(rounds):
+                for name, fn in (("bf16", bf16), ("fp8", fp8),
+                                 ("mxfp4", mxfp4)):
+                    for _ in range(10):
+                        fn()
+                    meds[name].append(_median(_event_times_us(fn, 100)))
+            mark = "" if block_m == rule else " (off-rule)"
+            print(f"| {T} | {block_m}{mark} | "
+                  + " | ".join(f"{min(m):.1f}..{max(m):.1f}"
+                               for m in meds.values())
+                  + f" | {min(meds['bf16']) / max(meds['mxfp4']):.2f}x"
+                  + f" | {min(meds['fp8']) / max(meds['mxfp4']):.2f}x |",
+                  flush=True)
+    active = 3 * H * inter  # weights of one expert
+    print("weight bytes per active expert: "
+          + ", ".join(f"{k} {active * v / 1e6:.2f} MB"
+                      for k, v in nbytes.items()))
+
+
 if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "all"
     torch.manual_seed(0)
@@ -1109,3 +1205,5 @@ if __name__ == "__main__":
         bench_bias_pipelining()
     if which in ("mxfp4", "all"):
         bench_mxfp4()
+    if which in ("mxfp4_moe", "all"):
+        bench_mxfp4_moe()

@@ -41,6 +41,11 @@ class ModelConfig:
     # run them on the grouped W4A16 GEMM. Off: an MoE model is refused in
     # mxfp4 mode. No effect on a dense model.
     mxfp4_moe_experts: bool = False
+    # with quantization == "mxfp4": how batches above MXFP4_MAX_M rows run.
+    # "bf16": dequant to a shared bf16 scratch + library GEMM. "mxfp8":
+    # activations quantised to MXFP8, scaled-MFMA HIP GEMM on the packed
+    # weights, no scratch. Smaller batches are the same in both.
+    mxfp4_activations: str = "bf16"
     # MoE (Qwen3-MoE family): num_experts 0 = dense MLP
     num_experts: int = 0
     num_experts_per_tok: int = 8

@@ -44,6 +44,14 @@ class ModelRunner:
             raise ValueError(
                 "mxfp4_moe_experts needs quantization='mxfp4', got "
                 f"{mc.quantization!r}")
+        if mc.mxfp4_activations not in ("bf16", "mxfp8"):
+            raise ValueError(
+                "mxfp4_activations must be 'bf16' or 'mxfp8', got "
+                f"{mc.mxfp4_activations!r}")
+        if mc.mxfp4_activations != "bf16" and mc.quantization != "mxfp4":
+            raise ValueError(
+                "mxfp4_activations needs quantization='mxfp4', got "
+                f"{mc.quantization!r}")
         if (mc.quantization == "mxfp4" and mc.is_moe
                 and not mc.mxfp4_moe_experts):
             # the experts are ~90 % of an MoE model's weights and would
@@ -85,12 +93,13 @@ class ModelRunner:
                 assert n > 0
             elif mc.quantization == "mxfp4":
                 # weight-only: bf16 weights (checkpoint or random init) are
-                # quantized here, activations stay bf16
+                # quantized here; activations stay bf16 unless
+                # mxfp4_activations == "mxfp8" (batches above MXFP4_MAX_M)
                 from fusioninfer_amd.quantization import (
                     convert_linear_to_mxfp4,
                 )
 
-                n = convert_linear_to_mxfp4(self.model)
+                n = convert_linear_to_mxfp4(self.model, mc.mxfp4_activations)
                 assert n > 0
                 if mc.is_moe:
                     from fusioninfer_amd.quantization import (

@@ -714,6 +714,102 @@ def mxfp4_dequant(w_packed, w_scale, out=None):
     return out
 
 
+def quant_mxfp8_rows(x, out=None):
+    """bf16 x [M, K] (contiguous, K % 128 == 0) -> (x_q [M, K] e4m3, x_scale
+    [M, K/32] uint8): MXFP8 along K, one e8m0 scale per 32 k, bit for bit
+    reference.mxfp8_quant_rows. `out` is an optional (x_q, x_scale) pair to
+    write into. Non-finite x is outside the contract."""
+    op = "quant_mxfp8_rows"
+    if x.dtype != torch.bfloat16:
+        raise ValueError(f"{op}: x must be bf16, got {x.dtype}")
+    if x.dim() != 2 or x.shape[1] < 128 or x.shape[1] % 128 != 0:
+        raise ValueError(
+            f"{op}: x must be [M, K] with K % 128 == 0, got {tuple(x.shape)}")
+    if not x.is_contiguous():
+        raise ValueError(f"{op}: x must be contiguous")
+    M, K = x.shape
+    if out is not None:
+        x_q, x_scale = out
+        if (x_q.dtype != torch.float8_e4m3fn or tuple(x_q.shape) != (M, K)
+                or x_scale.dtype != torch.uint8
+                or tuple(x_scale.shape) != (M, K // 32)
+                or x_q.device != x.device or x_scale.device != x.device
+                or not (x_q.is_contiguous() and x_scale.is_contiguous())):
+            raise ValueError(
+                f"{op}: out must be contiguous (e4m3 {(M, K)}, uint8 "
+                f"{(M, K // 32)}) tensors on {x.device}")
+    if x.is_cuda:
+        _require_native()
+        if out is None:
+            x_q = torch.empty((M, K), dtype=torch.float8_e4m3fn,
+                              device=x.device)
+            x_scale = torch.empty((M, K // 32), dtype=torch.uint8,
+                                  device=x.device)
+        if M > 0:
+            _C.quant_mxfp8_rows(x_q, x_scale, x)
+        return x_q, x_scale
+    res = ref.mxfp8_quant_rows(x)
+    if out is None:
+        return res
+    x_q.copy_(res[0])
+    x_scale.copy_(res[1])
+    return x_q, x_scale
+
+
+def mxfp4_mxfp8_linear(x_q, x_scale, w_packed, w_scale, bias=None, out=None):
+    """Scaled-MFMA linear on MXFP8 activations and MXFP4 weights:
+
+        out[m, n] = bf16( sum_k dq(x_q, x_scale)[m, k] * dq(W)[n, k]
+                          (+ bias[n]) )
+
+    with fp32 accumulation and one rounding. x_q [M, K] e4m3 and x_scale
+    [M, K/32] uint8 as quant_mxfp8_rows returns them; w_packed and w_scale
+    are the tensors of mxfp4_linear, unchanged. K % 128 == 0, N % 16 == 0,
+    any M >= 0. Static grid, no host sync, no workspace, no atomics:
+    hipGraph-capturable. K is summed in ascending 128-k steps, so a row's
+    bits depend only on its own operands. Defined while every partial sum is
+    finite in fp32; scale bytes are not scanned. Unsupported input raises
+    ValueError (no silent fallback)."""
+    op = "mxfp4_mxfp8_linear"
+    N, K = _check_mxfp4_weight(op, w_packed, w_scale)
+    if x_q.dtype != torch.float8_e4m3fn or x_scale.dtype != torch.uint8:
+        raise ValueError(
+            f"{op}: x_q must be float8_e4m3fn and x_scale uint8, got "
+            f"{x_q.dtype} and {x_scale.dtype}")
+    if x_q.dim() != 2 or x_q.shape[1] != K:
+        raise ValueError(f"{op}: x_q must be [M, {K}], got {tuple(x_q.shape)}")
+    M = x_q.shape[0]
+    if tuple(x_scale.shape) != (M, K // 32):
+        raise ValueError(
+            f"{op}: x_scale must be [M, K/32] = {(M, K // 32)}, got "
+            f"{tuple(x_scale.shape)}")
+    if not (x_q.is_contiguous() and x_scale.is_contiguous()):
+        raise ValueError(f"{op}: x_q and x_scale must be contiguous")
+    if x_q.device != w_packed.device or x_scale.device != x_q.device:
+        raise ValueError(
+            f"{op}: x_q, x_scale and the weights must share one device")
+    if bias is not None and (
+            bias.dtype != torch.bfloat16 or tuple(bias.shape) != (N,)
+            or bias.device != x_q.device or not bias.is_contiguous()):
+        raise ValueError(
+            f"{op}: bias must be a contiguous bf16 [{N}] tensor on "
+            f"{x_q.device}")
+    if out is not None:
+        _check_mxfp4_out(op, out, (M, N), x_q.device)
+    if x_q.is_cuda:
+        _require_native()
+        if out is None:
+            out = torch.empty((M, N), dtype=torch.bfloat16, device=x_q.device)
+        if M > 0:
+            _C.mxfp4_mxfp8_linear(out, x_q, x_scale, w_packed, w_scale, bias)
+        return out
+    res = ref.mxfp4_mxfp8_linear(x_q, x_scale, w_packed, w_scale, bias)
+    if out is None:
+        return res
+    out.copy_(res)
+    return out
+
+
 def moe_gemm_mxfp4(out, a, w_packed, w_scale, sorted_ids, expert_ids, n_valid,
                    block_m: int, gate_up: bool):
     """Grouped W4A16 GEMM over block-aligned expert segments (the moe_gemm

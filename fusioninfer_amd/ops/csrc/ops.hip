@@ -58,6 +58,12 @@ void launch_mxfp4_linear(u16*, const u16*, const unsigned char*,
                          hipStream_t);
 void launch_mxfp4_dequant(u16*, const unsigned char*, const unsigned char*,
                           int64_t, hipStream_t);
+void launch_mxfp4_mxfp8_linear(u16*, const unsigned char*,
+                               const unsigned char*, const unsigned char*,
+                               const unsigned char*, const u16*, int, int, int,
+                               hipStream_t);
+void launch_quant_mxfp8_rows(unsigned char*, unsigned char*, const u16*,
+                             int64_t, hipStream_t);
 void launch_moe_gemm_mxfp4(u16*, const u16*, const unsigned char*,
                            const unsigned char*, const int*, const int*,
                            const int*, int, int, int, int, bool, hipStream_t);
@@ -690,6 +696,87 @@ void mxfp4_dequant(at::Tensor out, at::Tensor w_packed, at::Tensor w_scale) {
       current_stream());
 }
 
+// x [M, K] bf16 -> x_q [M, K] e4m3 and x_scale [M, K/32] e8m0 (MXFP8 rows)
+void quant_mxfp8_rows(at::Tensor x_q, at::Tensor x_scale, at::Tensor x) {
+  CHECK_BF16_CUDA(x);
+  TORCH_CHECK(x_q.is_cuda() && x_scale.is_cuda() &&
+                  x_q.scalar_type() == at::kFloat8_e4m3fn &&
+                  x_scale.scalar_type() == at::kByte,
+              "quant_mxfp8_rows: x_q must be e4m3 and x_scale uint8, on GPU");
+  TORCH_CHECK(x.dim() == 2 && x_q.dim() == 2 && x_scale.dim() == 2 &&
+                  x.is_contiguous() && x_q.is_contiguous() &&
+                  x_scale.is_contiguous(),
+              "quant_mxfp8_rows: tensors must be 2-D and contiguous");
+  const int64_t M = x.size(0), K = x.size(1);
+  TORCH_CHECK(M >= 1 && K >= 128 && K % 128 == 0 && x_q.size(0) == M &&
+                  x_q.size(1) == K && x_scale.size(0) == M &&
+                  x_scale.size(1) == K / 32,
+              "quant_mxfp8_rows: need x [M, K], x_q [M, K], x_scale "
+              "[M, K/32], K % 128 == 0");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(x_q.data_ptr()) % 16 == 0,
+              "quant_mxfp8_rows: x and x_q must be 16-byte aligned");
+  TORCH_CHECK(x.get_device() == x_q.get_device() &&
+                  x.get_device() == x_scale.get_device(),
+              "quant_mxfp8_rows: tensors must share one device");
+  const int64_t nhalves = M * (K / 16);
+  TORCH_CHECK(nhalves / 256 < (1LL << 31) - 1, "quant_mxfp8_rows: too large");
+  fi::launch_quant_mxfp8_rows(static_cast<unsigned char*>(x_q.data_ptr()),
+                              static_cast<unsigned char*>(x_scale.data_ptr()),
+                              bf16_cptr(x), nhalves, current_stream());
+}
+
+void mxfp4_mxfp8_linear(at::Tensor out, at::Tensor x_q, at::Tensor x_scale,
+                        at::Tensor w_packed, at::Tensor w_scale,
+                        c10::optional<at::Tensor> bias) {
+  CHECK_BF16_CUDA(out);
+  int64_t N, K;
+  check_mxfp4_weight(w_packed, w_scale, &N, &K);
+  TORCH_CHECK(x_q.is_cuda() && x_scale.is_cuda() &&
+                  x_q.scalar_type() == at::kFloat8_e4m3fn &&
+                  x_scale.scalar_type() == at::kByte,
+              "mxfp4_mxfp8_linear: x_q must be e4m3 and x_scale uint8, on "
+              "GPU");
+  TORCH_CHECK(x_q.dim() == 2 && x_scale.dim() == 2 && out.dim() == 2 &&
+                  x_q.is_contiguous() && x_scale.is_contiguous() &&
+                  out.is_contiguous(),
+              "mxfp4_mxfp8_linear: x_q, x_scale and out must be 2-D and "
+              "contiguous");
+  const int64_t M = x_q.size(0);
+  TORCH_CHECK(M >= 1 && M <= 65535 * 128 && x_q.size(1) == K &&
+                  x_scale.size(0) == M && x_scale.size(1) == K / 32 &&
+                  out.size(0) == M && out.size(1) == N,
+              "mxfp4_mxfp8_linear: need x_q [M, K], x_scale [M, K/32], out "
+              "[M, N], 1 <= M <= 8388480");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x_q.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(out.data_ptr()) % 8 == 0,
+              "mxfp4_mxfp8_linear: x_q must be 16-byte and out 8-byte "
+              "aligned");
+  TORCH_CHECK(x_q.get_device() == out.get_device() &&
+                  x_q.get_device() == x_scale.get_device() &&
+                  x_q.get_device() == w_packed.get_device() &&
+                  x_q.get_device() == w_scale.get_device(),
+              "mxfp4_mxfp8_linear: tensors must share one device");
+  const u16* bias_p = nullptr;
+  if (bias.has_value()) {
+    CHECK_BF16_CUDA(*bias);
+    TORCH_CHECK(bias->dim() == 1 && bias->numel() == N &&
+                    bias->is_contiguous() &&
+                    bias->get_device() == x_q.get_device() &&
+                    reinterpret_cast<uintptr_t>(bias->data_ptr()) % 8 == 0,
+                "mxfp4_mxfp8_linear: bias must be a contiguous, 8-byte "
+                "aligned [N] bf16 tensor");
+    bias_p = bf16_cptr(*bias);
+  }
+  fi::launch_mxfp4_mxfp8_linear(
+      bf16_ptr(out), static_cast<const unsigned char*>(x_q.data_ptr()),
+      static_cast<const unsigned char*>(x_scale.data_ptr()),
+      static_cast<const unsigned char*>(w_packed.data_ptr()),
+      static_cast<const unsigned char*>(w_scale.data_ptr()), bias_p,
+      static_cast<int>(M), static_cast<int>(N), static_cast<int>(K),
+      current_stream());
+}
+
 // grouped W4A16 GEMM: w_packed [E, NB, K/2], w_scale [E, NB, K/32] uint8,
 // NB = 2N when gate_up; a = x [T, K] (gate_up) or act [PM, K]
 void moe_gemm_mxfp4(at::Tensor out, at::Tensor a, at::Tensor w_packed,
@@ -1066,6 +1153,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mxfp4_linear", &mxfp4_linear,
         "W4A16 linear on MXFP4 weights (bf16 in/out, fp32 accumulation)");
   m.def("mxfp4_dequant", &mxfp4_dequant, "expand MXFP4 weights to bf16");
+  m.def("quant_mxfp8_rows", &quant_mxfp8_rows,
+        "bf16 rows -> MXFP8 (e4m3 elements, one e8m0 scale per 32 k)");
+  m.def("mxfp4_mxfp8_linear", &mxfp4_mxfp8_linear,
+        "scaled-MFMA linear: MXFP8 activations x MXFP4 weights, bf16 out");
   m.def("moe_gemm_mxfp4", &moe_gemm_mxfp4,
         "grouped W4A16 GEMM over block-aligned expert segments with MXFP4 "
         "expert weights (gate_up=true fuses the SwiGLU epilogue)");

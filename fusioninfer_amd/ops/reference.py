@@ -734,6 +734,43 @@ def mxfp4_linear(x, w_packed, w_scale, bias=None) -> torch.Tensor:
     return out.to(torch.bfloat16)
 
 
+def mxfp8_quant_rows(x: torch.Tensor):
+    """bf16 [M, K] -> (e4m3 [M, K], e8m0 uint8 [M, K/32]): MXFP8 along K.
+    Per 32-k block: amax in fp32; s = 127 for an all-zero block, else
+    clamp(floor(log2(amax)) - 8 + 127, 8, 247) (8 = e4m3's emax); elements
+    are x * 2^(127 - s) (exact), clamped to +-448 (the scaled maximum lies in
+    [256, 512)) and rounded to nearest-even e4m3; zeros are stored as +0."""
+    M, K = x.shape
+    blocks = x.float().view(M, K // 32, 32)
+    amax = blocks.abs().amax(dim=-1)
+    _, e = torch.frexp(amax)
+    s = (e.to(torch.int32) - 1 - 8 + 127).clamp(8, 247)
+    s = torch.where(amax == 0, torch.full_like(s, 127), s)
+    inv = ((254 - s) << 23).view(torch.float32)
+    q = (blocks * inv.unsqueeze(-1)).clamp(-448.0, 448.0)
+    b = q.to(torch.float8_e4m3fn).view(torch.uint8)
+    b = torch.where(b == 0x80, torch.zeros_like(b), b)
+    return (b.view(M, K).view(torch.float8_e4m3fn),
+            s.to(torch.uint8).contiguous())
+
+
+def mxfp8_dequant(x_q: torch.Tensor, x_scale: torch.Tensor) -> torch.Tensor:
+    """MXFP8 -> bf16 [M, K], exact: e4m3 element times 2^(s - 127)."""
+    M, K = x_q.shape
+    scale = (x_scale.to(torch.int32) << 23).view(torch.float32)
+    out = x_q.float().view(M, K // 32, 32) * scale.unsqueeze(-1)
+    return out.view(M, K).to(torch.bfloat16)
+
+
+def mxfp4_mxfp8_linear(x_q, x_scale, w_packed, w_scale, bias=None):
+    """dq(x) [M, K] @ dq(W)^T (+ bias) in fp32, rounded to bf16 once."""
+    out = (mxfp8_dequant(x_q, x_scale).float()
+           @ mxfp4_dequant(w_packed, w_scale).float().t())
+    if bias is not None:
+        out = out + bias.float()
+    return out.to(torch.bfloat16)
+
+
 def moe_gemm_mxfp4(out, a, w_packed, w_scale, sorted_ids, expert_ids, n_valid,
                    block_m: int, gate_up: bool):
     """Grouped W4A16 GEMM on MXFP4 expert weights: the CPU path and the

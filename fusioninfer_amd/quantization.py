@@ -103,6 +103,11 @@ def convert_linear_to_fp8(module: nn.Module) -> int:
 # validate_mxfp4_scales rejects anything else, 0xFF (NaN) included — so every
 # dequantised value is zero or a normal bf16 and dequantisation is exact: the
 # W4A16 GEMM is "a bf16 GEMM with fp32 accumulation on dequant(W)".
+#
+# `--mxfp4-activations mxfp8` (opt-in) changes only the batches above
+# MXFP4_MAX_M rows: activations are quantised to MXFP8 (e4m3, one e8m0 scale
+# per 32 k) and multiplied with the packed weights by the scaled-MFMA HIP
+# GEMM (ops.mxfp4_mxfp8_linear), instead of dequant + library GEMM.
 
 MXFP4_BLOCK = 32
 # Largest M served by the weight-streaming HIP GEMM (ops.mxfp4_linear);
@@ -183,11 +188,23 @@ class _Mxfp4Scratch:
         return self.buf[: n * k].view(n, k)
 
 
-def convert_linear_to_mxfp4(module: nn.Module) -> int:
+MXFP4_ACTIVATIONS = ("bf16", "mxfp8")
+
+
+def convert_linear_to_mxfp4(module: nn.Module, activations: str = "bf16") -> int:
     """Convert every projection Linear in a CausalLM to MXFP4 storage:
     `weight` is replaced by the buffers `weight_packed` [N, K/2] and
     `weight_scale` [N, K/32] and the bf16 tensor is freed. Returns the
-    number of converted layers. lm_head/embedding stay bf16."""
+    number of converted layers. lm_head/embedding stay bf16.
+
+    `activations` picks the path of batches above MXFP4_MAX_M rows: "bf16"
+    expands the layer into the shared bf16 scratch and calls the library
+    GEMM; "mxfp8" quantises the activations to MXFP8 and runs the
+    scaled-MFMA HIP GEMM on the packed weights, so no scratch is reserved."""
+    if activations not in MXFP4_ACTIVATIONS:
+        raise ValueError(
+            f"mxfp4: activations must be one of {MXFP4_ACTIVATIONS}, got "
+            f"{activations!r}")
     from fusioninfer_amd.distributed.layers import (
         MergedColumnParallelLinear,
         RowParallelLinear,
@@ -207,7 +224,7 @@ def convert_linear_to_mxfp4(module: nn.Module) -> int:
                 f"{what} must be a multiple of 128 and the output rows a "
                 "multiple of 16")
     scratch = _Mxfp4Scratch()
-    if layers and layers[0].weight.is_cuda:
+    if activations == "bf16" and layers and layers[0].weight.is_cuda:
         scratch.reserve(max(m.weight.numel() for m in layers),
                         layers[0].weight.device)
     for m in layers:
@@ -217,7 +234,7 @@ def convert_linear_to_mxfp4(module: nn.Module) -> int:
         del m.weight
         m.register_buffer("weight_packed", packed, persistent=False)
         m.register_buffer("weight_scale", scale, persistent=False)
-        m.forward = _make_mxfp4_forward(m, scratch)
+        m.forward = _make_mxfp4_forward(m, scratch, activations)
     return len(layers)
 
 
@@ -275,7 +292,7 @@ def convert_moe_experts_to_mxfp4(module: nn.Module) -> int:
     return len(mlps)
 
 
-def _make_mxfp4_forward(m, scratch):
+def _make_mxfp4_forward(m, scratch, activations="bf16"):
     from fusioninfer_amd import ops
 
     is_row_parallel = hasattr(m, "in_per_rank")
@@ -284,7 +301,12 @@ def _make_mxfp4_forward(m, scratch):
 
     def fwd(x):
         x = x.contiguous()
-        if x.is_cuda and x.shape[0] > MXFP4_MAX_M:
+        if activations == "mxfp8" and x.shape[0] > MXFP4_MAX_M:
+            # GPU: two HIP kernels; CPU: their reference ops
+            x_q, x_scale = ops.quant_mxfp8_rows(x)
+            out = ops.mxfp4_mxfp8_linear(x_q, x_scale, m.weight_packed,
+                                         m.weight_scale, bias)
+        elif x.is_cuda and x.shape[0] > MXFP4_MAX_M:
             w = ops.mxfp4_dequant(m.weight_packed, m.weight_scale,
                                   out=scratch.view(N, K))
             out = F.linear(x, w, bias)

@@ -49,6 +49,18 @@ def parse_args(argv=None):
                         "are not faster at batch 1); prefill expert GEMMs "
                         "(batch >= 1024 tokens) are about 2x slower "
                         "(profiles/r13_mxfp4_moe.md)")
+    p.add_argument("--mxfp4-activations", choices=["bf16", "mxfp8"],
+                   default="bf16",
+                   help="with --quantization mxfp4: how batches above 32 "
+                        "rows (prefill, wide decode) run. bf16: expand the "
+                        "layer to a shared bf16 scratch and call the library "
+                        "GEMM. mxfp8: quantise activations to MXFP8 and run "
+                        "the scaled-MFMA HIP GEMM on the packed weights; no "
+                        "scratch is reserved, activations carry e4m3 "
+                        "rounding. As measured it is faster than bf16 mode "
+                        "only on gate_up up to 256 rows and slower elsewhere "
+                        "(profiles/r14_mxfp4_scaled_mfma.md). Batches up to "
+                        "32 rows are identical in both")
     p.add_argument("--sampler-backend", choices=["torch", "fused"],
                    default="torch",
                    help="fused: one HIP sampling launch per step "
@@ -136,6 +148,7 @@ def build_engine_config(args):
     mc.model_path = args.model_path
     mc.quantization = args.quantization
     mc.mxfp4_moe_experts = args.mxfp4_moe_experts
+    mc.mxfp4_activations = args.mxfp4_activations
     speculative = None
     if args.speculative_config:
         from fusioninfer_amd.engine.spec_decode import SpeculativeConfig

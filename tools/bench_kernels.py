@@ -1022,13 +1022,19 @@ class _OneTarget:
         self.layers = [{"t": (a, b, scales)}]
 
 
-def bench_mxfp4():
+def bench_mxfp4(rounds=3):
     """The four Qwen3-8B projections at decode-to-prefill batch sizes:
-    mxfp4_linear, mxfp4_dequant + F.linear, bf16 F.linear and the fp8
-    _scaled_mm path. Median device-event time per call; GB/s is the
-    weight bytes each path has to stream (4.25 / 16 / 8 bits per weight;
-    dequant + F.linear also writes and re-reads the bf16 copy) over that
-    time."""
+    mxfp4_linear (up to M = 512), mxfp4_dequant + F.linear, bf16 F.linear,
+    the fp8 _scaled_mm path, and the scaled-MFMA path of
+    --mxfp4-activations mxfp8: quant_mxfp8_rows + mxfp4_mxfp8_linear, and
+    that GEMM alone with its achieved TFLOP/s (2 M N K over its time). GB/s
+    is the weight bytes each of the first four paths has to stream (4.25 /
+    16 / 8 bits per weight; dequant + F.linear also writes and re-reads the
+    bf16 copy) over its time. Median device-event time of 100 calls,
+    `rounds` alternating repetitions per shape; the cell is the median
+    repetition. The last column is the fastest dequant + F.linear
+    repetition over the slowest quant + GEMM repetition: above 1 the new
+    pair won every time."""
     import torch.nn.functional as F
 
     from fusioninfer_amd import ops
@@ -1040,8 +1046,9 @@ def bench_mxfp4():
     print("\n## MXFP4 W4A16 projections (Qwen3-8B shapes, median us, "
           "weight GB/s)")
     print("| layer NxK | M | mxfp4_linear | dequant+linear | bf16 linear | "
-          "fp8 scaled_mm | bf16/mxfp4 |")
-    print("|---|---|---|---|---|---|---|")
+          "fp8 scaled_mm | quant+a8 GEMM | a8 GEMM alone (TFLOP/s) | "
+          "bf16/mxfp4_linear | dequant fastest / a8 pair slowest |")
+    print("|---|---|---|---|---|---|---|---|---|---|")
     for name, N, K in shapes:
         w = torch.randn(N, K, device="cuda", dtype=torch.bfloat16) * 0.02
         packed, scale = quantize_weight_mxfp4(w)
@@ -1049,28 +1056,48 @@ def bench_mxfp4():
         scratch = torch.empty(N, K, device="cuda", dtype=torch.bfloat16)
         b4 = N * K // 2 + N * K // 32
         b16 = 2 * N * K
-        for M in (1, 8, 32, 64, 128, 256, 512):
+        nbytes = (b4, b4 + 2 * b16, b16, N * K)
+        for M in (1, 8, 32, 64, 128, 256, 512, 1024, 2048, 8192):
             x = torch.randn(M, K, device="cuda", dtype=torch.bfloat16)
             out = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
+            xq, xs = ops.quant_mxfp8_rows(x)
 
             def dq_linear():
                 ops.mxfp4_dequant(packed, scale, out=scratch)
                 return F.linear(x, scratch)
 
-            cols = []
-            for fn, nbytes in (
-                (lambda: ops.mxfp4_linear(x, packed, scale, out=out), b4),
-                (dq_linear, b4 + 2 * b16),
-                (lambda: F.linear(x, w), b16),
-                (lambda: fp8_linear(x, w8, s8), N * K),
-            ):
-                for _ in range(10):
-                    fn()
-                us = _median(_event_times_us(fn, 100))
-                cols.append((us, nbytes / us / 1e3))
-            print(f"| {name} {N}x{K} | {M} | "
-                  + " | ".join(f"{u:.1f} ({g:.0f})" for u, g in cols)
-                  + f" | {cols[2][0] / cols[0][0]:.2f}x |", flush=True)
+            def a8_pair():
+                ops.quant_mxfp8_rows(x, out=(xq, xs))
+                ops.mxfp4_mxfp8_linear(xq, xs, packed, scale, out=out)
+
+            fns = [
+                lambda: ops.mxfp4_linear(x, packed, scale, out=out),
+                dq_linear,
+                lambda: F.linear(x, w),
+                lambda: fp8_linear(x, w8, s8),
+                a8_pair,
+                lambda: ops.mxfp4_mxfp8_linear(xq, xs, packed, scale, out=out),
+            ]
+            if M > 512:
+                fns[0] = None  # the streaming kernel is a decode kernel
+            meds = [[] for _ in fns]
+            for _ in range(rounds):
+                for i, fn in enumerate(fns):
+                    if fn is None:
+                        continue
+                    for _ in range(10):
+                        fn()
+                    meds[i].append(_median(_event_times_us(fn, 100)))
+            us = [_median(m) if m else None for m in meds]
+            cells = ["-" if u is None else f"{u:.1f}" for u in us]
+            for i, nb in enumerate(nbytes):
+                if us[i] is not None:
+                    cells[i] += f" ({nb / us[i] / 1e3:.0f})"
+            cells[5] += f" ({2.0 * M * N * K / us[5] / 1e6:.0f})"
+            ratio = "-" if us[0] is None else f"{us[2] / us[0]:.2f}x"
+            print(f"| {name} {N}x{K} | {M} | " + " | ".join(cells)
+                  + f" | {ratio} | {min(meds[1]) / max(meds[4]):.2f}x |",
+                  flush=True)
 
 
 def bench_mxfp4_moe(rounds=3):

@@ -75,14 +75,17 @@ def silu_and_mul(x: torch.Tensor) -> torch.Tensor:
 # The fp8 serving mode quantizes activations per-token for torch._scaled_mm;
 # done eagerly that costs more than the fp8 GEMM saves, so quantization is
 # fused into the producing kernel (norm / SwiGLU) or done in one pass
-# (quant_fp8_rows for the attention output).
+# (quant_fp8_rows for the attention output). Inputs may have any number of
+# leading dimensions; the scales come back with the input's shape less its
+# last dimension, one per row.
 
 def rms_norm_fp8(x: torch.Tensor, weight: torch.Tensor, eps: float):
     """Returns (x_fp8 [T, H] e4m3, scales [T] fp32)."""
     if x.is_cuda:
         _require_native()
         out = torch.empty(x.shape, dtype=torch.float8_e4m3fn, device=x.device)
-        scales = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+        scales = torch.empty(x.shape[:-1], dtype=torch.float32,
+                             device=x.device)
         _C.rms_norm_fp8(out, scales, x, weight, eps)
         return out, scales
     return ref.rms_norm_fp8(x, weight, eps)
@@ -93,7 +96,8 @@ def fused_add_rms_norm_fp8(x, residual, weight, eps: float):
     if x.is_cuda:
         _require_native()
         out = torch.empty(x.shape, dtype=torch.float8_e4m3fn, device=x.device)
-        scales = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+        scales = torch.empty(x.shape[:-1], dtype=torch.float32,
+                             device=x.device)
         _C.fused_add_rms_norm_fp8(out, scales, x, residual, weight, eps)
         return out, scales, residual
     return ref.fused_add_rms_norm_fp8(x, residual, weight, eps)
@@ -107,7 +111,8 @@ def silu_and_mul_fp8(x: torch.Tensor):
         out = torch.empty(
             (*x.shape[:-1], inter), dtype=torch.float8_e4m3fn, device=x.device
         )
-        scales = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+        scales = torch.empty(x.shape[:-1], dtype=torch.float32,
+                             device=x.device)
         _C.silu_and_mul_fp8(out, scales, x)
         return out, scales
     return ref.silu_and_mul_fp8(x)
@@ -118,7 +123,8 @@ def quant_fp8_rows(x: torch.Tensor):
     if x.is_cuda:
         _require_native()
         out = torch.empty(x.shape, dtype=torch.float8_e4m3fn, device=x.device)
-        scales = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+        scales = torch.empty(x.shape[:-1], dtype=torch.float32,
+                             device=x.device)
         _C.quant_fp8_rows(out, scales, x)
         return out, scales
     return ref.quant_fp8_rows(x)
@@ -138,9 +144,14 @@ def rope_qk_norm_(
     k_weight: Optional[torch.Tensor] = None,
     eps: float = 1e-6,
 ):
-    """Fused optional per-head RMSNorm + NeoX RoPE, in-place. Returns (q, k)."""
+    """Fused optional per-head RMSNorm + NeoX RoPE, in-place. Returns (q, k).
+    The kernel covers head_dim 64 and 128; anything else raises ValueError
+    on the GPU."""
     if q.is_cuda:
         _require_native()
+        if head_dim not in (64, 128):
+            raise ValueError(
+                f"rope_qk_norm_: head_dim must be 64 or 128, got {head_dim}")
         _C.rope_qk_norm(
             q, k, q_weight, k_weight, cos_sin, positions,
             num_q_heads, num_kv_heads, head_dim, eps,

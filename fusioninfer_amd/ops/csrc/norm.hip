@@ -135,7 +135,8 @@ void launch_rms_norm(void* out, float* out_scales, const u16* in,
     FI_CASE(7)
     FI_CASE(8)
     default:
-      // hidden > 16384 unsupported by this kernel family
+      // hidden > 16384 is unsupported by this kernel family; unreachable:
+      // check_rms_norm() in ops.hip rejects it in every rms_norm* binding
       abort();
   }
 #undef FI_CASE

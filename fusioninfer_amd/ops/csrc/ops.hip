@@ -112,47 +112,109 @@ bool cache_is_fp8(const at::Tensor& t) {
   return t.scalar_type() == at::kFloat8_e4m3fn;
 }
 
+bool aligned16(const at::Tensor& t) {
+  return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+}
+
+// Row shape of the rms_norm* ops. The kernels hold a row in registers
+// (ITERS <= 8 iterations of 2048 columns) and move 8 bf16 per lane, so
+// hidden must be a multiple of 8 and at most 16384; the launcher has no
+// kernel for anything else.
+struct RowDims {
+  int tokens, hidden;
+};
+
+RowDims check_rms_norm(const char* op, const at::Tensor& input,
+                       const at::Tensor& weight) {
+  TORCH_CHECK(input.dim() >= 1 && input.is_contiguous(), op,
+              ": input must be contiguous");
+  const int64_t hidden = input.size(-1);
+  TORCH_CHECK(hidden >= 8 && hidden % 8 == 0 && hidden <= 16384, op,
+              ": hidden must be a multiple of 8 in [8, 16384], got ", hidden);
+  const int64_t tokens = input.numel() / hidden;
+  TORCH_CHECK(tokens < (1LL << 31), op, ": too many rows");
+  TORCH_CHECK(weight.is_cuda() && weight.scalar_type() == at::kBFloat16, op,
+              ": weight must be a bf16 GPU tensor");
+  TORCH_CHECK(weight.is_contiguous() && weight.numel() == hidden, op,
+              ": weight must be contiguous with ", hidden, " elements, got ",
+              weight.numel());
+  TORCH_CHECK(weight.get_device() == input.get_device(), op,
+              ": weight and input must share one device");
+  TORCH_CHECK(aligned16(input) && aligned16(weight), op,
+              ": input and weight must be 16-byte aligned");
+  return {static_cast<int>(tokens), static_cast<int>(hidden)};
+}
+
+// `other` is indexed exactly as `input` is: same shape, device, alignment
+void check_same_rows(const char* op, const char* name, const at::Tensor& other,
+                     const at::Tensor& input) {
+  TORCH_CHECK(other.is_contiguous() && other.sizes() == input.sizes() &&
+                  other.get_device() == input.get_device() && aligned16(other),
+              op, ": ", name,
+              " must be contiguous, 16-byte aligned, of the input's shape and "
+              "on its device");
+}
+
+// fp8 output [rows, cols] and its per-row scales [rows]
+void check_fp8_out(const char* op, const at::Tensor& out,
+                   const at::Tensor& scales, const at::Tensor& input,
+                   int64_t rows, int64_t cols) {
+  TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kFloat8_e4m3fn &&
+                  out.is_contiguous(),
+              op, ": out must be a contiguous float8_e4m3fn GPU tensor");
+  TORCH_CHECK(out.dim() >= 1 && out.size(-1) == cols &&
+                  out.numel() == rows * cols,
+              op, ": out must hold ", rows, " rows of ", cols, " columns");
+  TORCH_CHECK(scales.is_cuda() && scales.scalar_type() == at::kFloat &&
+                  scales.is_contiguous() && scales.numel() == rows,
+              op, ": out_scales must be a contiguous fp32 GPU tensor of ",
+              rows, " elements");
+  TORCH_CHECK(out.get_device() == input.get_device() &&
+                  scales.get_device() == input.get_device(),
+              op, ": tensors must share one device");
+  // the kernels store 4 bytes at a time
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(out.data_ptr()) % 4 == 0, op,
+              ": out must be 4-byte aligned");
+}
+
+// the attention launchers have kernels for these two head sizes only
+void check_attn_head_dim(const char* op, int64_t head_dim) {
+  TORCH_CHECK(head_dim == 64 || head_dim == 128, op,
+              ": head_dim must be 64 or 128, got ", head_dim);
+}
+
 void rms_norm(at::Tensor out, at::Tensor input, at::Tensor weight, double eps) {
   CHECK_BF16_CUDA(out);
   CHECK_BF16_CUDA(input);
-  TORCH_CHECK(input.is_contiguous() && out.is_contiguous());
-  const int hidden = input.size(-1);
-  const int tokens = input.numel() / hidden;
+  const RowDims d = check_rms_norm("rms_norm", input, weight);
+  check_same_rows("rms_norm", "out", out, input);
   fi::launch_rms_norm<false, false>(bf16_ptr(out), nullptr, bf16_cptr(input),
                                     nullptr, bf16_cptr(weight),
-                                    static_cast<float>(eps), tokens, hidden,
-                                    current_stream());
+                                    static_cast<float>(eps), d.tokens,
+                                    d.hidden, current_stream());
 }
 
 void fused_add_rms_norm(at::Tensor input, at::Tensor residual,
                         at::Tensor weight, double eps) {
   CHECK_BF16_CUDA(input);
   CHECK_BF16_CUDA(residual);
-  TORCH_CHECK(input.is_contiguous() && residual.is_contiguous());
-  const int hidden = input.size(-1);
-  const int tokens = input.numel() / hidden;
+  const RowDims d = check_rms_norm("fused_add_rms_norm", input, weight);
+  check_same_rows("fused_add_rms_norm", "residual", residual, input);
   // in-place: residual += input; input = rmsnorm(residual)
   fi::launch_rms_norm<true, false>(bf16_ptr(input), nullptr, bf16_cptr(input),
                                    bf16_ptr(residual), bf16_cptr(weight),
-                                   static_cast<float>(eps), tokens, hidden,
-                                   current_stream());
+                                   static_cast<float>(eps), d.tokens,
+                                   d.hidden, current_stream());
 }
-
-#define CHECK_FP8_OUT(o, s)                                                  \
-  TORCH_CHECK((o).scalar_type() == at::kFloat8_e4m3fn && (o).is_cuda() &&    \
-              (o).is_contiguous());                                          \
-  TORCH_CHECK((s).scalar_type() == at::kFloat && (s).is_cuda())
 
 void rms_norm_fp8(at::Tensor out, at::Tensor out_scales, at::Tensor input,
                   at::Tensor weight, double eps) {
   CHECK_BF16_CUDA(input);
-  CHECK_FP8_OUT(out, out_scales);
-  TORCH_CHECK(input.is_contiguous());
-  const int hidden = input.size(-1);
-  const int tokens = input.numel() / hidden;
+  const RowDims d = check_rms_norm("rms_norm_fp8", input, weight);
+  check_fp8_out("rms_norm_fp8", out, out_scales, input, d.tokens, d.hidden);
   fi::launch_rms_norm<false, true>(
       out.data_ptr(), out_scales.data_ptr<float>(), bf16_cptr(input), nullptr,
-      bf16_cptr(weight), static_cast<float>(eps), tokens, hidden,
+      bf16_cptr(weight), static_cast<float>(eps), d.tokens, d.hidden,
       current_stream());
 }
 
@@ -161,51 +223,64 @@ void fused_add_rms_norm_fp8(at::Tensor out, at::Tensor out_scales,
                             at::Tensor weight, double eps) {
   CHECK_BF16_CUDA(input);
   CHECK_BF16_CUDA(residual);
-  CHECK_FP8_OUT(out, out_scales);
-  TORCH_CHECK(input.is_contiguous() && residual.is_contiguous());
-  const int hidden = input.size(-1);
-  const int tokens = input.numel() / hidden;
+  const RowDims d = check_rms_norm("fused_add_rms_norm_fp8", input, weight);
+  check_same_rows("fused_add_rms_norm_fp8", "residual", residual, input);
+  check_fp8_out("fused_add_rms_norm_fp8", out, out_scales, input, d.tokens,
+                d.hidden);
   // residual += input (in place); out = fp8(rmsnorm(residual))
   fi::launch_rms_norm<true, true>(
       out.data_ptr(), out_scales.data_ptr<float>(), bf16_cptr(input),
-      bf16_ptr(residual), bf16_cptr(weight), static_cast<float>(eps), tokens,
-      hidden, current_stream());
+      bf16_ptr(residual), bf16_cptr(weight), static_cast<float>(eps),
+      d.tokens, d.hidden, current_stream());
+}
+
+// rows of `cols` bf16 columns (SwiGLU: 2 * cols per input row), 8 per lane
+RowDims check_quant_rows(const char* op, const at::Tensor& input,
+                         int64_t in_cols_per_col) {
+  TORCH_CHECK(input.dim() >= 1 && input.is_contiguous() && aligned16(input),
+              op, ": input must be contiguous and 16-byte aligned");
+  const int64_t width = input.size(-1);
+  TORCH_CHECK(width >= 8 * in_cols_per_col &&
+                  width % (8 * in_cols_per_col) == 0 && width < (1LL << 30),
+              op, ": input width must be a positive multiple of ",
+              8 * in_cols_per_col, ", got ", width);
+  const int64_t rows = input.numel() / width;
+  TORCH_CHECK(rows < (1LL << 31), op, ": too many rows");
+  return {static_cast<int>(rows), static_cast<int>(width / in_cols_per_col)};
 }
 
 void silu_and_mul_fp8(at::Tensor out, at::Tensor out_scales, at::Tensor input) {
   CHECK_BF16_CUDA(input);
-  CHECK_FP8_OUT(out, out_scales);
-  TORCH_CHECK(input.is_contiguous());
-  const int inter = out.size(-1);
-  TORCH_CHECK(input.size(-1) == 2 * inter);
-  TORCH_CHECK(inter % 8 == 0);
+  const RowDims d = check_quant_rows("silu_and_mul_fp8", input, 2);
+  check_fp8_out("silu_and_mul_fp8", out, out_scales, input, d.tokens,
+                d.hidden);
   fi::launch_row_quant_fp8<true>(
       static_cast<unsigned char*>(out.data_ptr()),
-      out_scales.data_ptr<float>(), bf16_cptr(input),
-      input.numel() / (2 * inter), inter, current_stream());
+      out_scales.data_ptr<float>(), bf16_cptr(input), d.tokens, d.hidden,
+      current_stream());
 }
 
 void quant_fp8_rows(at::Tensor out, at::Tensor out_scales, at::Tensor input) {
   CHECK_BF16_CUDA(input);
-  CHECK_FP8_OUT(out, out_scales);
-  TORCH_CHECK(input.is_contiguous());
-  const int cols = input.size(-1);
-  TORCH_CHECK(cols % 8 == 0);
+  const RowDims d = check_quant_rows("quant_fp8_rows", input, 1);
+  check_fp8_out("quant_fp8_rows", out, out_scales, input, d.tokens, d.hidden);
   fi::launch_row_quant_fp8<false>(
       static_cast<unsigned char*>(out.data_ptr()),
-      out_scales.data_ptr<float>(), bf16_cptr(input), input.numel() / cols,
-      cols, current_stream());
+      out_scales.data_ptr<float>(), bf16_cptr(input), d.tokens, d.hidden,
+      current_stream());
 }
 
 void silu_and_mul(at::Tensor out, at::Tensor input) {
   CHECK_BF16_CUDA(out);
   CHECK_BF16_CUDA(input);
-  TORCH_CHECK(input.is_contiguous() && out.is_contiguous());
-  const int inter = out.size(-1);
-  TORCH_CHECK(input.size(-1) == 2 * inter);
-  TORCH_CHECK(inter % 8 == 0);
-  fi::launch_silu_and_mul(bf16_ptr(out), bf16_cptr(input),
-                          input.numel() / (2 * inter), inter,
+  const RowDims d = check_quant_rows("silu_and_mul", input, 2);
+  TORCH_CHECK(out.is_contiguous() && aligned16(out) && out.dim() >= 1 &&
+                  out.size(-1) == d.hidden &&
+                  out.numel() == static_cast<int64_t>(d.tokens) * d.hidden &&
+                  out.get_device() == input.get_device(),
+              "silu_and_mul: out must be a contiguous, 16-byte aligned [",
+              d.tokens, ", ", d.hidden, "] tensor on the input's device");
+  fi::launch_silu_and_mul(bf16_ptr(out), bf16_cptr(input), d.tokens, d.hidden,
                           current_stream());
 }
 
@@ -218,15 +293,53 @@ void rope_qk_norm(at::Tensor q, at::Tensor k,
   CHECK_BF16_CUDA(k);
   TORCH_CHECK(cos_sin.scalar_type() == at::kFloat && cos_sin.is_cuda());
   TORCH_CHECK(positions.scalar_type() == at::kInt && positions.is_cuda());
+  TORCH_CHECK(k.get_device() == q.get_device() &&
+                  cos_sin.get_device() == q.get_device() &&
+                  positions.get_device() == q.get_device(),
+              "rope_qk_norm: q, k, cos_sin and positions must share one "
+              "device");
   // q/k may be row-strided slices of the fused qkv projection output
   TORCH_CHECK(q.dim() == 2 && k.dim() == 2);
   TORCH_CHECK(q.stride(1) == 1 && k.stride(1) == 1);
-  const int tokens = q.size(0);
+  // the launcher has kernels for these two only
+  TORCH_CHECK(head_dim == 64 || head_dim == 128,
+              "rope_qk_norm: head_dim must be 64 or 128, got ", head_dim);
+  TORCH_CHECK(num_q_heads >= 1 && num_kv_heads >= 1 &&
+                  num_q_heads + num_kv_heads <= 65535,
+              "rope_qk_norm: bad head counts");
+  const int64_t tokens = q.size(0);
+  TORCH_CHECK(tokens < (1LL << 31) && k.size(0) == tokens &&
+                  q.size(1) == num_q_heads * head_dim &&
+                  k.size(1) == num_kv_heads * head_dim,
+              "rope_qk_norm: need q [T, Hq*D] and k [T, Hk*D]");
+  TORCH_CHECK(cos_sin.is_contiguous() && cos_sin.dim() == 2 &&
+                  cos_sin.size(1) == head_dim,
+              "rope_qk_norm: cos_sin must be a contiguous [P, D] tensor");
+  TORCH_CHECK(positions.is_contiguous() && positions.numel() == tokens,
+              "rope_qk_norm: positions must be a contiguous [T] tensor");
+  // every lane moves one 4-byte bf16 pair
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(q.data_ptr()) % 4 == 0 &&
+                  reinterpret_cast<uintptr_t>(k.data_ptr()) % 4 == 0 &&
+                  q.stride(0) % 2 == 0 && k.stride(0) % 2 == 0,
+              "rope_qk_norm: q and k rows must be 4-byte aligned");
+  auto weight_ptr = [&](const c10::optional<at::Tensor>& w) -> const u16* {
+    if (!w) return nullptr;
+    CHECK_BF16_CUDA(*w);
+    TORCH_CHECK(w->is_contiguous() && w->numel() == head_dim &&
+                    w->get_device() == q.get_device() &&
+                    reinterpret_cast<uintptr_t>(w->data_ptr()) % 4 == 0,
+                "rope_qk_norm: a norm weight must be a contiguous [D] bf16 "
+                "tensor on q's device");
+    return bf16_cptr(*w);
+  };
+  const u16* qw = weight_ptr(q_weight);
+  const u16* kw = weight_ptr(k_weight);
+  if (tokens == 0) return;
   fi::launch_rope_qk_norm(
-      bf16_ptr(q), bf16_ptr(k), q.stride(0), k.stride(0),
-      q_weight ? bf16_cptr(*q_weight) : nullptr,
-      k_weight ? bf16_cptr(*k_weight) : nullptr, cos_sin.data_ptr<float>(),
-      positions.data_ptr<int>(), tokens, num_q_heads, num_kv_heads, head_dim,
+      bf16_ptr(q), bf16_ptr(k), q.stride(0), k.stride(0), qw, kw,
+      cos_sin.data_ptr<float>(), positions.data_ptr<int>(),
+      static_cast<int>(tokens), static_cast<int>(num_q_heads),
+      static_cast<int>(num_kv_heads), static_cast<int>(head_dim),
       static_cast<float>(eps), current_stream());
 }
 
@@ -366,6 +479,14 @@ void paged_attention_decode(at::Tensor out, at::Tensor q, at::Tensor k_cache,
   const int num_heads = q.size(1);
   const int head_dim = q.size(2);
   const int num_kv_heads = k_cache.size(1);
+  check_attn_head_dim("paged_attention_decode", head_dim);
+  {
+    const int g = num_kv_heads > 0 ? num_heads / num_kv_heads : 0;
+    TORCH_CHECK(num_kv_heads > 0 && g * num_kv_heads == num_heads &&
+                    (g == 1 || g == 2 || g == 4 || g == 8),
+                "paged_attention_decode: need Hq == Hk * G with G in "
+                "{1, 2, 4, 8}, got Hq=", num_heads, " Hk=", num_kv_heads);
+  }
   TORCH_CHECK(k_cache.size(2) == 16, "cache block_size must be 16");
   TORCH_CHECK(q.stride(2) == 1 && q.stride(1) == head_dim);
   TORCH_CHECK(out.is_contiguous() && out.sizes() == q.sizes(),
@@ -401,6 +522,7 @@ void prefill_attention(at::Tensor out, at::Tensor q, at::Tensor k,
   const int num_q_heads = q.size(1);
   const int head_dim = q.size(2);
   const int num_kv_heads = k.size(1);
+  check_attn_head_dim("prefill_attention", head_dim);
   TORCH_CHECK(q.stride(2) == 1 && q.stride(1) == head_dim);
   TORCH_CHECK(k.stride(2) == 1 && k.stride(1) == head_dim);
   TORCH_CHECK(v.stride(2) == 1 && v.stride(1) == head_dim);
@@ -436,6 +558,7 @@ void prefill_attention_paged(at::Tensor out, at::Tensor q, at::Tensor k_cache,
   const int num_q_heads = q.size(1);
   const int head_dim = q.size(2);
   const int num_kv_heads = k_cache.size(1);
+  check_attn_head_dim("prefill_attention_paged", head_dim);
   TORCH_CHECK(k_cache.size(2) == 16, "cache block_size must be 16");
   TORCH_CHECK(q.stride(2) == 1 && q.stride(1) == head_dim);
   TORCH_CHECK(out.is_contiguous() && out.sizes() == q.sizes(),

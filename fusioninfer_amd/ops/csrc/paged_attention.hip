@@ -620,11 +620,14 @@ void launch_paged_attn_decode(u16* out, float* ml_ws, float* acc_ws,
       case 2: return launch(d, std::integral_constant<int, 2>{});
       case 4: return launch(d, std::integral_constant<int, 4>{});
       case 8: return launch(d, std::integral_constant<int, 8>{});
+      // unreachable: the paged_attention_decode binding in ops.hip checks
+      // Hq == Hk * G with G in {1, 2, 4, 8}
       default: abort();
     }
   };
   if (head_dim == 128) launch_group(std::integral_constant<int, 128>{});
   else if (head_dim == 64) launch_group(std::integral_constant<int, 64>{});
+  // unreachable: check_attn_head_dim() in ops.hip, called by that binding
   else abort();
 }
 

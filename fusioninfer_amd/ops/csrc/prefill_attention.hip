@@ -558,7 +558,9 @@ void launch_prefill_attn(u16* out, const u16* q, const void* k, const void* v,
                          max_blocks, q_stride, k_stride, v_stride,            \
                          num_q_heads, num_kv_heads, scale, adj);              \
   } while (0)
-  if (fp8 && !paged) abort();  // fp8 KV is a cache format; dense is bf16
+  // fp8 KV is a cache format; dense is bf16. Unreachable: the dense
+  // prefill_attention binding in ops.hip passes fp8 = false
+  if (fp8 && !paged) abort();
   if (head_dim == 128) {
     if (paged) {
       if (fp8) FI_PF_LAUNCH(128, true, true);
@@ -574,6 +576,8 @@ void launch_prefill_attn(u16* out, const u16* q, const void* k, const void* v,
       FI_PF_LAUNCH(64, false, false);
     }
   } else {
+    // unreachable: check_attn_head_dim() in ops.hip, called by both
+    // prefill bindings
     abort();
   }
 #undef FI_PF_LAUNCH

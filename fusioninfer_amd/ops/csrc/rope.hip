@@ -93,7 +93,9 @@ void launch_rope_qk_norm(u16* q, u16* k, int64_t q_stride, int64_t k_stride,
                        q_stride, k_stride, q_weight, k_weight, cos_sin,
                        positions, num_q_heads, eps);
   } else {
-    abort();  // head_dim ∈ {64, 128}
+    // unreachable: the rope_qk_norm binding in ops.hip checks
+    // head_dim == 64 || head_dim == 128
+    abort();
   }
 }
 
@@ -287,7 +289,9 @@ void launch_rope_qk_norm_cache(
   } else if (head_dim == 64) {
     if (fp8) FI_ROPE_CACHE(64, true); else FI_ROPE_CACHE(64, false);
   } else {
-    abort();  // head_dim ∈ {64, 128}, checked by the binding
+    // unreachable: the rope_qk_norm_cache binding in ops.hip checks
+    // head_dim == 64 || head_dim == 128
+    abort();
   }
 #undef FI_ROPE_CACHE
 }

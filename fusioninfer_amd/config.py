@@ -46,6 +46,12 @@ class ModelConfig:
     # activations quantised to MXFP8, scaled-MFMA HIP GEMM on the packed
     # weights, no scratch. Smaller batches are the same in both.
     mxfp4_activations: str = "bf16"
+    # with mxfp4_moe_experts: how the experts run once a batch is routed at
+    # block_m 128 (T * top_k >= 256 * E_local, i.e. prefill). "bf16": the
+    # grouped W4A16 GEMM. "mxfp8": x quantised to MXFP8 once per token, the
+    # grouped scaled-MFMA GEMM with the SwiGLU + MXFP8 epilogue, then the
+    # scaled-MFMA down GEMM. Smaller batches (decode) are the same in both.
+    mxfp4_moe_activations: str = "bf16"
     # MoE (Qwen3-MoE family): num_experts 0 = dense MLP
     num_experts: int = 0
     num_experts_per_tok: int = 8

@@ -52,6 +52,13 @@ class ModelRunner:
             raise ValueError(
                 "mxfp4_activations needs quantization='mxfp4', got "
                 f"{mc.quantization!r}")
+        if mc.mxfp4_moe_activations not in ("bf16", "mxfp8"):
+            raise ValueError(
+                "mxfp4_moe_activations must be 'bf16' or 'mxfp8', got "
+                f"{mc.mxfp4_moe_activations!r}")
+        if mc.mxfp4_moe_activations != "bf16" and not mc.mxfp4_moe_experts:
+            raise ValueError(
+                "mxfp4_moe_activations needs mxfp4_moe_experts")
         if (mc.quantization == "mxfp4" and mc.is_moe
                 and not mc.mxfp4_moe_experts):
             # the experts are ~90 % of an MoE model's weights and would
@@ -108,7 +115,8 @@ class ModelRunner:
 
                     # drops the experts' bf16 weights and MFMA pack before
                     # the KV cache is sized
-                    assert convert_moe_experts_to_mxfp4(self.model) > 0
+                    assert convert_moe_experts_to_mxfp4(
+                        self.model, mc.mxfp4_moe_activations) > 0
         if mc.quantization not in (None, "fp8", "mxfp4"):
             raise ValueError(f"unknown quantization {mc.quantization!r}")
         if self.is_cuda and os.environ.get(

@@ -219,6 +219,7 @@ class MoEMLP(nn.Module):
         # set by quantization.convert_moe_experts_to_mxfp4: experts live in
         # gate_up_packed / gate_up_scale / down_packed / down_scale only
         self.mxfp4 = False
+        self.mxfp4_activations = "bf16"  # or "mxfp8": block_m 128 batches
         H, inter = cfg.hidden_size, cfg.moe_intermediate_size
         base = torch.initial_seed() % (2**62)
         dev = torch.empty(0).device  # honor the ambient torch.device context
@@ -623,14 +624,31 @@ class MoEMLP(nn.Module):
             topi, block_m
         )
         inter = self.down_packed.shape[2] * 2
-        act = torch.empty(PM, inter, dtype=x.dtype, device=x.device)
-        ops.moe_gemm_mxfp4(act, x, self.gate_up_packed, self.gate_up_scale,
-                           sorted_ids, expert_ids, n_valid, block_m,
-                           gate_up=True)
-        y = torch.empty(PM, H, dtype=x.dtype, device=x.device)
-        ops.moe_gemm_mxfp4(y, act, self.down_packed, self.down_scale,
-                           sorted_ids, expert_ids, n_valid, block_m,
-                           gate_up=False)
+        if block_m == 128 and self.mxfp4_activations == "mxfp8":
+            # x is quantised once per token and gathered by the kernel; the
+            # act tensor exists only as MXFP8, written by the gate_up
+            # epilogue (block_m 128 is ops.MOE_A8_BLOCK_M)
+            x_q, x_scale = ops.quant_mxfp8_rows(x)
+            act_q = torch.empty(PM, inter, dtype=torch.float8_e4m3fn,
+                                device=x.device)
+            act_scale = torch.empty(PM, inter // 32, dtype=torch.uint8,
+                                    device=x.device)
+            ops.moe_gemm_mxfp4_mxfp8(
+                act_q, x_q, x_scale, self.gate_up_packed, self.gate_up_scale,
+                sorted_ids, expert_ids, n_valid, True, act_scale)
+            y = torch.empty(PM, H, dtype=x.dtype, device=x.device)
+            ops.moe_gemm_mxfp4_mxfp8(
+                y, act_q, act_scale, self.down_packed, self.down_scale,
+                sorted_ids, expert_ids, n_valid, False)
+        else:
+            act = torch.empty(PM, inter, dtype=x.dtype, device=x.device)
+            ops.moe_gemm_mxfp4(act, x, self.gate_up_packed,
+                               self.gate_up_scale, sorted_ids, expert_ids,
+                               n_valid, block_m, gate_up=True)
+            y = torch.empty(PM, H, dtype=x.dtype, device=x.device)
+            ops.moe_gemm_mxfp4(y, act, self.down_packed, self.down_scale,
+                               sorted_ids, expert_ids, n_valid, block_m,
+                               gate_up=False)
         out = torch.empty(T, H, dtype=x.dtype, device=x.device)
         ops.moe_combine(out, y, pos, topv.reshape(-1).float().contiguous())
         return ps.tp_all_reduce(out)

@@ -899,6 +899,116 @@ def moe_gemm_mxfp4(out, a, w_packed, w_scale, sorted_ids, expert_ids, n_valid,
                               expert_ids, n_valid, block_m, gate_up)
 
 
+MOE_A8_BLOCK_M = 128  # the only m-tile of moe_gemm_mxfp4_mxfp8
+
+
+def moe_gemm_mxfp4_mxfp8(out, a_q, a_scale, w_packed, w_scale, sorted_ids,
+                         expert_ids, n_valid, gate_up: bool, out_scale=None):
+    """Grouped scaled-MFMA GEMM over block-aligned expert segments (the
+    moe_gemm contract at block_m = MOE_A8_BLOCK_M = 128) with MXFP4 expert
+    weights and MXFP8 activations; neither operand is expanded.
+
+    a_q e4m3 / a_scale uint8 as quant_mxfp8_rows returns them: x [T, K] and
+    [T, K/32] with gate_up (rows gathered via sorted_ids, so x is quantised
+    once per token), act [PM, K] and [PM, K/32] without. w_packed [E, NB,
+    K/2] and w_scale [E, NB, K/32] are the tensors of moe_gemm_mxfp4, NB =
+    2N when gate_up. K % 128 == 0, PM a positive multiple of 128.
+
+    gate_up=False: out [PM, N] bf16, N % 16 == 0, out_scale must be None;
+    returns out. A row equals mxfp4_mxfp8_linear on that row and its
+    expert's weights bit for bit.
+    gate_up=True: silu(gate) * up is rounded to bf16 and quantised to MXFP8
+    in the epilogue, bit for bit reference.mxfp8_quant_rows of that bf16 row:
+    out [PM, N] float8_e4m3fn and out_scale [PM, N/32] uint8, N % 32 == 0;
+    returns (out, out_scale).
+
+    Tiles at or past n_valid are not touched. Static grid, no host sync, no
+    workspace, no atomics: hipGraph-capturable. A row's bits depend only on
+    its own operands. Unsupported input raises ValueError before any launch
+    (no silent fallback)."""
+    op = "moe_gemm_mxfp4_mxfp8"
+    BM = MOE_A8_BLOCK_M
+    want_out = torch.float8_e4m3fn if gate_up else torch.bfloat16
+    if out.dtype != want_out:
+        raise ValueError(
+            f"{op}: out must be {want_out} with gate_up={gate_up}, got "
+            f"{out.dtype}")
+    if a_q.dtype != torch.float8_e4m3fn or a_scale.dtype != torch.uint8:
+        raise ValueError(
+            f"{op}: a_q must be float8_e4m3fn and a_scale uint8, got "
+            f"{a_q.dtype} and {a_scale.dtype}")
+    if w_packed.dtype != torch.uint8 or w_scale.dtype != torch.uint8:
+        raise ValueError(
+            f"{op}: w_packed and w_scale must be uint8, got "
+            f"{w_packed.dtype} and {w_scale.dtype}")
+    if (sorted_ids.dtype != torch.int32 or expert_ids.dtype != torch.int32
+            or n_valid.dtype != torch.int32):
+        raise ValueError(
+            f"{op}: sorted_ids, expert_ids and n_valid must be int32")
+    if out.dim() != 2 or a_q.dim() != 2 or a_scale.dim() != 2 \
+            or w_packed.dim() != 3 or w_scale.dim() != 3 \
+            or sorted_ids.dim() != 1 or expert_ids.dim() != 1 \
+            or n_valid.numel() != 1:
+        raise ValueError(
+            f"{op}: need out [PM, N], a_q [rows, K], a_scale [rows, K/32], "
+            "w_packed [E, NB, K/2], w_scale [E, NB, K/32], sorted_ids [PM], "
+            "expert_ids [PM/128] and a one-element n_valid")
+    tensors = [out, a_q, a_scale, w_packed, w_scale, sorted_ids, expert_ids,
+               n_valid]
+    PM, N = out.shape
+    K = a_q.shape[1]
+    if gate_up:
+        if out_scale is None or out_scale.dtype != torch.uint8 \
+                or tuple(out_scale.shape) != (PM, N // 32):
+            raise ValueError(
+                f"{op}: gate_up needs out_scale, a uint8 "
+                f"[{PM}, {N // 32}] tensor")
+        tensors.append(out_scale)
+    elif out_scale is not None:
+        raise ValueError(f"{op}: out_scale must be None without gate_up")
+    if any(t.device != out.device for t in tensors):
+        raise ValueError(f"{op}: all tensors must share one device")
+    if not all(t.is_contiguous() for t in tensors):
+        raise ValueError(f"{op}: all tensors must be contiguous")
+    NB = 2 * N if gate_up else N
+    nq = 32 if gate_up else 16
+    if K < 128 or K % 128 != 0 or N < nq or N % nq != 0:
+        raise ValueError(
+            f"{op}: unsupported shape N={N} K={K} with gate_up={gate_up} "
+            f"(need K % 128 == 0 and N % {nq} == 0)")
+    E = w_packed.shape[0]
+    if E < 1 or tuple(w_packed.shape) != (E, NB, K // 2) \
+            or tuple(w_scale.shape) != (E, NB, K // 32):
+        raise ValueError(
+            f"{op}: need w_packed [E, {NB}, {K // 2}] and w_scale "
+            f"[E, {NB}, {K // 32}], got {tuple(w_packed.shape)} and "
+            f"{tuple(w_scale.shape)}")
+    if sorted_ids.numel() % BM != 0 or sorted_ids.numel() != PM or PM < BM:
+        raise ValueError(
+            f"{op}: sorted_ids must hold PM = {PM} slots, a positive "
+            f"multiple of {BM}; got {sorted_ids.numel()}")
+    if expert_ids.numel() < PM // BM:
+        raise ValueError(
+            f"{op}: expert_ids must cover {PM // BM} m-tiles, got "
+            f"{expert_ids.numel()}")
+    rows = a_q.shape[0]
+    if rows < 1 or (not gate_up and rows != PM) \
+            or tuple(a_scale.shape) != (rows, K // 32):
+        raise ValueError(
+            f"{op}: a_q must be [{PM}, {K}] without gate_up and have at "
+            f"least one row with it, and a_scale [rows, {K // 32}]; got "
+            f"{tuple(a_q.shape)} and {tuple(a_scale.shape)}")
+    if out.is_cuda:
+        _require_native()
+        _C.moe_gemm_mxfp4_mxfp8(out, a_q, a_scale, w_packed, w_scale,
+                                sorted_ids, expert_ids, n_valid, gate_up,
+                                out_scale)
+        return (out, out_scale) if gate_up else out
+    return ref.moe_gemm_mxfp4_mxfp8(out, a_q, a_scale, w_packed, w_scale,
+                                    sorted_ids, expert_ids, n_valid, gate_up,
+                                    out_scale)
+
+
 # ---------------------------------------------------------------- sampling
 
 def sample_tokens(logits, temperature, top_k, top_p, min_p, rng):

@@ -35,6 +35,7 @@ SOURCES = [
     "mxfp4_gemm.hip",
     "mxfp8_gemm.hip",
     "moe_mxfp4_gemm.hip",
+    "moe_mxfp8_gemm.hip",
 ]
 
 

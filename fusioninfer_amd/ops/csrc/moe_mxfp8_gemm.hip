@@ -1,0 +1,366 @@
+// Grouped MXFP4 x MXFP8 scaled-MFMA GEMM for MoE experts at prefill
+// (gfx950): the block_m 128 path of `--mxfp4-moe-activations mxfp8`.
+//
+//   down:    out[slot, n] = bf16( sum_k dq(a)[slot, k] * dq(W[e])[n, k] )
+//   gate_up: (out, out_scale)[slot] = mxfp8_quant_rows( bf16( swiglu(
+//                sum_k dq(a)[row(slot), k] * dq(W[e])[n, k],
+//                sum_k dq(a)[row(slot), k] * dq(W[e])[N + n, k] ) ) )
+//
+// joins the block-aligned grouped-GEMM contract of moe_mxfp4_gemm.hip
+// (sorted_ids / expert_ids / the n_valid device scalar, static grid; an
+// m-tile is 128 padded slots of one expert) and the operand movement of
+// mxfp4_mxfp8_gemm_kernel (mxfp8_gemm.hip, whose header documents the lane
+// layout of v_mfma_scale_f32_16x16x128_f8f6f4). Expert weights are the
+// tensors moe_gemm_mxfp4 reads, unchanged: w_packed [E, NB, K/2] and w_scale
+// [E, NB, K/32], NB = 2N (gate rows, then up rows) for gate_up. Neither
+// operand is expanded, nothing is repacked, and nothing is indexed from
+// weight or scale data.
+//
+// Operand movement, both instances. W is srcA and the activation is srcB.
+// Per 128-k step a wave loads its 4 W fragments (16 B per lane, one MX block
+// each) and their scale bytes from HBM/L2 straight to VGPRs, one step ahead.
+// The 128-row x 128-byte activation panel of a step is staged through
+// registers into LDS once per workgroup (144 B padded rows, double-buffered,
+// one barrier per step), and so are the 4 activation scale bytes of every
+// row for that step (one dword per row; a lane shifts out the byte of its
+// MX block). Panel row i is a_q[row(i)] with row(i) = sorted_ids[slot] for
+// gate_up (x is quantised once per token and gathered here; pad slots carry
+// row 0) and row(i) = slot for down; the ids are read once per workgroup,
+// before the K loop. The loop runs two steps per trip over two named operand
+// sets, without a branch in the trip, held in order by scheduling fences; an
+// odd last step is peeled.
+//
+// Down (GATE_UP = false): 128 x 128 tile, the waves 2 x 2 with a 4 x 4 block
+// of 16x16 accumulators each; 8 B bf16 stores. Columns past N are clamped in
+// bounds when loaded and never stored.
+//
+// Gate_up (GATE_UP = true): 128 slots x 64 act columns; the workgroup reads
+// 64 gate rows and the matching 64 up rows of W. The waves sit 2 x 2, each
+// owning 64 slots x 32 act columns: 4 m-fragments x (2 gate + 2 up)
+// n-fragments, the register budget of the down instance. With W as srcA a
+// lane holds m = l & 15 and n = 4 (l >> 4) ... + 3 of every fragment, so the
+// gate and the up value of one act element sit in the same lane and element,
+// and a wave owns whole 32-column MX blocks of an act row: the epilogue
+// needs no LDS. Per m-fragment: v = bf16(swiglu(g, u)); block amax over the
+// lane's 2 x 4 values and across the four lane groups (shfl_xor 16, 32); the
+// scale byte, scaling, clamp, convert and -0 rule of quant_mxfp8_rows; one
+// 4 B store per lane per n-fragment, and lane group 0 stores the scale byte.
+// The output equals reference.mxfp8_quant_rows on the bf16 act row, bit for
+// bit; the bf16 act tensor never exists.
+//
+// Determinism: every accumulator sums the K steps in ascending order and
+// nothing is split or combined across waves, so a (token, expert) row's bits
+// depend on its own operands only, and a down row equals mxfp4_mxfp8_linear
+// on that row and its expert's weights bit for bit. No atomics, no
+// workspace, no host sync; a workgroup whose m-tile is >= *n_valid returns
+// before any barrier.
+
+#include <hip/hip_runtime.h>
+
+#include <type_traits>
+
+#include "common.h"
+
+namespace fi {
+
+namespace {
+
+typedef __attribute__((ext_vector_type(4))) float floatx4;
+typedef __attribute__((ext_vector_type(4))) u32 u32x4;
+typedef __attribute__((ext_vector_type(8))) int intx8;
+typedef __attribute__((ext_vector_type(2))) short short2_t;
+
+constexpr int kBlockM = 128;     // slots of an m-tile
+constexpr int kRowBytes = 144;   // LDS row: 128 B of e4m3 + 16 B pad
+constexpr int kFmtFp8 = 0;       // e4m3
+constexpr int kFmtFp4 = 4;       // e2m1
+
+// nothing is scheduled across this point
+#if defined(__HIP_DEVICE_COMPILE__)
+#define FI_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
+#else
+#define FI_SCHED_FENCE()
+#endif
+
+// D = A(fp4, 16 x 128) * B(fp8, 128 x 16) + C with per-lane block scales
+FI_DEV floatx4 mfma_w4a8(u32x4 w, u32 wscale, intx8 x, u32 xscale,
+                         floatx4 acc) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const intx8 a = {static_cast<int>(w[0]), static_cast<int>(w[1]),
+                   static_cast<int>(w[2]), static_cast<int>(w[3]), 0, 0, 0, 0};
+  return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
+      a, x, acc, kFmtFp4, kFmtFp8, 0, static_cast<int>(wscale), 0,
+      static_cast<int>(xscale));
+#else
+  return acc;
+#endif
+}
+
+// same expression as moe_mxfp4_gemm_kernel's epilogue
+FI_DEV float swiglu(float g, float u) { return (g / (1.f + __expf(-g))) * u; }
+
+// four scaled, clamped values -> four e4m3 bytes (v[0] lowest), -0 as +0
+FI_DEV u32 pack_fp8x4(const float* v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  union {
+    u32 u;
+    short2_t s;
+  } c;
+  c.u = 0;
+  // the block scale is already applied (exactly) because the clamp needs
+  // the scaled value; the convert itself runs at scale 1
+  c.s = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(c.s, v[0], v[1], 1.0f, false);
+  c.s = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(c.s, v[2], v[3], 1.0f, true);
+  u32 w = c.u;
+  if ((w & 0x0000007fu) == 0) w &= 0xffffff00u;
+  if ((w & 0x00007f00u) == 0) w &= 0xffff00ffu;
+  if ((w & 0x007f0000u) == 0) w &= 0xff00ffffu;
+  if ((w & 0x7f000000u) == 0) w &= 0x00ffffffu;
+  return w;
+#else
+  return 0;
+#endif
+}
+
+template <bool GATE_UP>
+__global__ __launch_bounds__(256, 2) void moe_mxfp4_mxfp8_gemm_kernel(
+    void* __restrict__ out_v,               // [PM, N] bf16, or e4m3 (GATE_UP)
+    unsigned char* __restrict__ out_scale,  // GATE_UP: [PM, N/32] e8m0
+    const unsigned char* __restrict__ aq,   // GATE_UP: [T, K]; else [PM, K]
+    const unsigned char* __restrict__ asc,  // same rows, [., K/32] e8m0
+    const unsigned char* __restrict__ wq,   // [E, NB, K/2]
+    const unsigned char* __restrict__ ws,   // [E, NB, K/32]
+    const int* __restrict__ sorted_ids,     // [PM] token row per padded slot
+    const int* __restrict__ expert_ids,     // [PM/128] local expert per tile
+    const int* __restrict__ n_valid,        // device scalar: real tile count
+    const int K, const int N) {
+  const int mtile = blockIdx.x;
+  if (mtile >= *n_valid) return;
+
+  // columns of out per workgroup and per wave
+  constexpr int kTileN = GATE_UP ? 64 : 128;
+  constexpr int kWaveN = kTileN / 2;
+  const int tid = threadIdx.x;
+  const int lane = tid % kWaveSize;
+  const int wave = tid / kWaveSize;
+  const int r = lane & 15;
+  const int g = lane >> 4;
+  const int slot0 = mtile * kBlockM;
+  const int wm = 64 * (wave >> 1);                            // first slot
+  const int wn = blockIdx.y * kTileN + kWaveN * (wave & 1);   // first column
+  const int nsteps = K / 128;
+  const int NB = GATE_UP ? 2 * N : N;
+  const int64_t wrow0 = static_cast<int64_t>(expert_ids[mtile]) * NB;
+
+  __shared__ __attribute__((aligned(16))) unsigned char
+      xl[2][kBlockM * kRowBytes];
+  // the step's 4 scale bytes of every row; the upper 128 entries only give
+  // threads 128 ... 255 somewhere to store, so that no store is predicated
+  __shared__ u32 sl[2][2 * kBlockM];
+
+  // panel staging: thread -> rows tid / 8 + 32 i, 16 B chunk tid % 8; scale
+  // staging: thread -> row tid % 128
+  const unsigned char* xg[4];
+  int xo[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int row = (tid >> 3) + 32 * i;
+    const int src = GATE_UP ? sorted_ids[slot0 + row] : slot0 + row;
+    xg[i] = aq + static_cast<int64_t>(src) * K + 16 * (tid & 7);
+    xo[i] = row * kRowBytes + 16 * (tid & 7);
+  }
+  const unsigned char* sg;
+  {
+    const int row = tid & (kBlockM - 1);
+    const int src = GATE_UP ? sorted_ids[slot0 + row] : slot0 + row;
+    sg = asc + static_cast<int64_t>(src) * (K / 32);
+  }
+  // W fragments and their scale bytes: lane -> row r, MX block g of the step
+  const unsigned char* wp[4];
+  const unsigned char* wsp[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    // gate_up: fragments 0, 1 are gate rows, 2, 3 the matching up rows
+    const int col = GATE_UP ? wn + 16 * (j & 1) + r : wn + 16 * j + r;
+    const int64_t n =
+        wrow0 + (GATE_UP && j >= 2 ? N : 0) + min(col, N - 1);
+    wp[j] = wq + n * (K / 2) + 16 * g;
+    wsp[j] = ws + n * (K / 32) + g;
+  }
+  // x fragment: bytes 16 g ... + 15 and 64 + 16 g ... + 15 of the row's step
+  const int xfrag = (wm + r) * kRowBytes + 16 * g;
+
+  floatx4 acc[4][4];  // [n fragment][m fragment]
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) acc[j][i] = floatx4{0.f, 0.f, 0.f, 0.f};
+
+  // two named operand sets: step s computes from set s & 1 while the loads
+  // of step s + 1 land in the other one. The panel and its scales are loaded
+  // two steps ahead (stage[s & 1] holds step s + 2).
+  u32x4 stage[2][4], wv[2][4];
+  u32 sstage[2], wsc[2][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    stage[0][i] = *reinterpret_cast<const u32x4*>(xg[i]);
+    stage[1][i] = *reinterpret_cast<const u32x4*>(
+        xg[i] + min(1, nsteps - 1) * 128);
+  }
+  sstage[0] = *reinterpret_cast<const u32*>(sg);
+  sstage[1] = *reinterpret_cast<const u32*>(sg + min(1, nsteps - 1) * 4);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    wv[0][j] = *reinterpret_cast<const u32x4*>(wp[j]);
+    wsc[0][j] = wsp[j][0];
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    *reinterpret_cast<u32x4*>(&xl[0][xo[i]]) = stage[0][i];
+  sl[0][tid] = sstage[0];
+  __syncthreads();
+
+  // the 16 MFMAs of one step: operand set and LDS buffers P
+  auto mfmas = [&](auto P) {
+    constexpr int p = decltype(P)::value;
+    const unsigned char* buf = xl[p];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const u32x4 lo =
+          *reinterpret_cast<const u32x4*>(buf + xfrag + 16 * i * kRowBytes);
+      const u32x4 hi = *reinterpret_cast<const u32x4*>(
+          buf + xfrag + 16 * i * kRowBytes + 64);
+      const intx8 xv = {static_cast<int>(lo[0]), static_cast<int>(lo[1]),
+                        static_cast<int>(lo[2]), static_cast<int>(lo[3]),
+                        static_cast<int>(hi[0]), static_cast<int>(hi[1]),
+                        static_cast<int>(hi[2]), static_cast<int>(hi[3])};
+      // byte g of the row's dword (one v_bfe_u32)
+      const u32 xsc = (sl[p][wm + 16 * i + r] >> (8 * g)) & 0xffu;
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        acc[j][i] = mfma_w4a8(wv[p][j], wsc[p][j], xv, xsc, acc[j][i]);
+    }
+  };
+  // one full step s of parity P. Past the end the last step is loaded again
+  // and stored into the idle buffers: in bounds, never read.
+  auto step = [&](auto P, int s) {
+    constexpr int p = decltype(P)::value;
+    const int sn = min(s + 1, nsteps - 1);
+    const int sx = min(s + 2, nsteps - 1);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      stage[p][i] = *reinterpret_cast<const u32x4*>(xg[i] + sx * 128);
+    sstage[p] = *reinterpret_cast<const u32*>(sg + sx * 4);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      wv[p ^ 1][j] = *reinterpret_cast<const u32x4*>(wp[j] + sn * 64);
+      wsc[p ^ 1][j] = wsp[j][sn * 4];
+    }
+    FI_SCHED_FENCE();  // the loads are issued before the MFMAs ...
+    mfmas(P);
+    FI_SCHED_FENCE();  // ... and waited for only after them
+    // buffers p ^ 1 were last read in step s - 1, before its barrier
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      *reinterpret_cast<u32x4*>(&xl[p ^ 1][xo[i]]) = stage[p ^ 1][i];
+    sl[p ^ 1][tid] = sstage[p ^ 1];
+    __syncthreads();
+  };
+  // Two steps per trip with no branch between them, so the fences hold both
+  // halves in place. An odd last step is peeled: its operands are already in
+  // set 0 and buffers 0.
+  using P0 = std::integral_constant<int, 0>;
+  using P1 = std::integral_constant<int, 1>;
+  for (int s = 0; s + 1 < nsteps; s += 2) {
+    step(P0{}, s);
+    step(P1{}, s + 1);
+  }
+  if (nsteps & 1) mfmas(P0{});
+
+  // lane -> slot r of each m fragment, columns 4 g ... + 3 of each n
+  // fragment
+  if constexpr (!GATE_UP) {
+    u16* out = static_cast<u16*>(out_v);
+    // N % 16 == 0, so a fragment is stored whole or not at all
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int n = wn + 16 * j + 4 * g;
+      if (n < N) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int64_t slot = slot0 + wm + 16 * i + r;
+          bf16x4 o;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) o.h[e] = f32_to_bf16(acc[j][i][e]);
+          *reinterpret_cast<bf16x4*>(out + slot * N + n) = o;
+        }
+      }
+    }
+  } else {
+    unsigned char* out = static_cast<unsigned char*>(out_v);
+    // N % 32 == 0, so a wave's MX block of act columns is whole or absent
+    // (wave-uniform; every barrier is behind us)
+    if (wn < N) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int64_t slot = slot0 + wm + 16 * i + r;
+        float v[2][4];
+        float amax = 0.f;
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            v[j][e] = bf16_to_f32(
+                f32_to_bf16(swiglu(acc[j][i][e], acc[j + 2][i][e])));
+            amax = fmaxf(amax, fabsf(v[j][e]));
+          }
+        amax = fmaxf(amax, __shfl_xor(amax, 16, 64));
+        amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
+        // quant_mxfp8_rows' rule: floor(log2(amax)) is the exponent field;
+        // a subnormal amax reads 0 and clamps to 8 as its true exponent would
+        int s = static_cast<int>((__float_as_uint(amax) >> 23) & 0xff) - 8;
+        s = min(max(s, 8), 247);
+        if (amax == 0.f) s = 127;
+        const float inv = __uint_as_float(static_cast<u32>(254 - s) << 23);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          // the convert gives NaN past 448 instead of saturating: clamp first
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            v[j][e] = fminf(fmaxf(v[j][e] * inv, -448.f), 448.f);
+          *reinterpret_cast<u32*>(out + slot * N + wn + 16 * j + 4 * g) =
+              pack_fp8x4(v[j]);
+        }
+        if (g == 0)
+          out_scale[slot * (N / 32) + wn / 32] = static_cast<unsigned char>(s);
+      }
+    }
+  }
+}
+
+}  // namespace
+
+// K % 128 == 0, N % 16 == 0 (N % 32 == 0 with gate_up), max_mtiles tiles of
+// 128 slots (checked by the binding). The grid is static and tiles at or
+// past *n_valid leave at once.
+void launch_moe_gemm_mxfp4_mxfp8(void* out, unsigned char* out_scale,
+                                 const unsigned char* aq,
+                                 const unsigned char* asc,
+                                 const unsigned char* wq,
+                                 const unsigned char* ws,
+                                 const int* sorted_ids, const int* expert_ids,
+                                 const int* n_valid, int max_mtiles, int K,
+                                 int N, bool gate_up, hipStream_t stream) {
+  if (gate_up)
+    moe_mxfp4_mxfp8_gemm_kernel<true>
+        <<<dim3(max_mtiles, ceil_div(N, 64)), 256, 0, stream>>>(
+            out, out_scale, aq, asc, wq, ws, sorted_ids, expert_ids, n_valid, K,
+            N);
+  else
+    moe_mxfp4_mxfp8_gemm_kernel<false>
+        <<<dim3(max_mtiles, ceil_div(N, 128)), 256, 0, stream>>>(
+            out, out_scale, aq, asc, wq, ws, sorted_ids, expert_ids, n_valid, K,
+            N);
+}
+
+}  // namespace fi

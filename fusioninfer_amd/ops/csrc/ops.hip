@@ -67,6 +67,10 @@ void launch_quant_mxfp8_rows(unsigned char*, unsigned char*, const u16*,
 void launch_moe_gemm_mxfp4(u16*, const u16*, const unsigned char*,
                            const unsigned char*, const int*, const int*,
                            const int*, int, int, int, int, bool, hipStream_t);
+void launch_moe_gemm_mxfp4_mxfp8(void*, unsigned char*, const unsigned char*,
+                                 const unsigned char*, const unsigned char*,
+                                 const unsigned char*, const int*, const int*,
+                                 const int*, int, int, int, bool, hipStream_t);
 void launch_sample_tokens(int64_t*, const float*, const float*, const int*,
                           const float*, const float*, const int64_t*, int,
                           int, hipStream_t);
@@ -966,6 +970,105 @@ void moe_gemm_mxfp4(at::Tensor out, at::Tensor a, at::Tensor w_packed,
       gate_up, current_stream());
 }
 
+// grouped scaled-MFMA GEMM, m-tiles of 128 slots: a_q e4m3 and a_scale e8m0
+// are x [T, .] (gate_up, gathered via sorted_ids) or act [PM, .]; weights as
+// moe_gemm_mxfp4. gate_up writes MXFP8 (out e4m3 [PM, N], out_scale [PM,
+// N/32]), down writes bf16 and takes no out_scale
+void moe_gemm_mxfp4_mxfp8(at::Tensor out, at::Tensor a_q, at::Tensor a_scale,
+                          at::Tensor w_packed, at::Tensor w_scale,
+                          at::Tensor sorted_ids, at::Tensor expert_ids,
+                          at::Tensor n_valid, bool gate_up,
+                          c10::optional<at::Tensor> out_scale) {
+  constexpr int64_t BM = 128;
+  TORCH_CHECK(out.is_cuda() && out.dim() == 2 && out.is_contiguous() &&
+                  out.scalar_type() ==
+                      (gate_up ? at::kFloat8_e4m3fn : at::kBFloat16),
+              "moe_gemm_mxfp4_mxfp8: out must be a contiguous 2-D GPU tensor, "
+              "e4m3 with gate_up and bf16 without");
+  TORCH_CHECK(a_q.is_cuda() && a_scale.is_cuda() &&
+                  a_q.scalar_type() == at::kFloat8_e4m3fn &&
+                  a_scale.scalar_type() == at::kByte && a_q.dim() == 2 &&
+                  a_scale.dim() == 2 && a_q.is_contiguous() &&
+                  a_scale.is_contiguous(),
+              "moe_gemm_mxfp4_mxfp8: a_q must be e4m3 and a_scale uint8, 2-D "
+              "and contiguous on GPU");
+  TORCH_CHECK(w_packed.is_cuda() && w_scale.is_cuda() &&
+                  w_packed.scalar_type() == at::kByte &&
+                  w_scale.scalar_type() == at::kByte &&
+                  w_packed.dim() == 3 && w_scale.dim() == 3 &&
+                  w_packed.is_contiguous() && w_scale.is_contiguous(),
+              "moe_gemm_mxfp4_mxfp8: weights must be contiguous 3-D uint8 on "
+              "GPU");
+  TORCH_CHECK(sorted_ids.is_cuda() && expert_ids.is_cuda() &&
+                  n_valid.is_cuda() && sorted_ids.scalar_type() == at::kInt &&
+                  expert_ids.scalar_type() == at::kInt &&
+                  n_valid.scalar_type() == at::kInt &&
+                  sorted_ids.is_contiguous() && expert_ids.is_contiguous() &&
+                  n_valid.numel() == 1,
+              "moe_gemm_mxfp4_mxfp8: sorted_ids, expert_ids, n_valid must be "
+              "contiguous int32 on GPU");
+  const int64_t K = a_q.size(1);
+  const int64_t N = out.size(1);
+  const int64_t PM = out.size(0);
+  const int64_t NB = gate_up ? 2 * N : N;
+  const int64_t nq = gate_up ? 32 : 16;
+  TORCH_CHECK(K >= 128 && K % 128 == 0 && N >= nq && N % nq == 0 &&
+                  K < (1LL << 31) && NB < (1LL << 31) &&
+                  (N + 63) / 64 <= 65535,
+              "moe_gemm_mxfp4_mxfp8: need K % 128 == 0 and N % 16 == 0 "
+              "(N % 32 == 0 with gate_up)");
+  TORCH_CHECK(PM >= BM && PM % BM == 0 && PM < (1LL << 31),
+              "moe_gemm_mxfp4_mxfp8: padded rows must be a multiple of 128");
+  TORCH_CHECK(w_packed.size(0) >= 1 && w_packed.size(1) == NB &&
+                  w_packed.size(2) == K / 2 &&
+                  w_scale.size(0) == w_packed.size(0) &&
+                  w_scale.size(1) == NB && w_scale.size(2) == K / 32,
+              "moe_gemm_mxfp4_mxfp8: need w_packed [E, NB, K/2] and w_scale "
+              "[E, NB, K/32]");
+  TORCH_CHECK(expert_ids.numel() >= PM / BM && sorted_ids.numel() >= PM &&
+                  a_q.size(0) >= 1 && (gate_up || a_q.size(0) >= PM) &&
+                  a_scale.size(0) == a_q.size(0) && a_scale.size(1) == K / 32,
+              "moe_gemm_mxfp4_mxfp8: sorted_ids / expert_ids / a_q too short "
+              "or a_scale not [rows, K/32]");
+  unsigned char* out_scale_p = nullptr;
+  if (gate_up) {
+    TORCH_CHECK(out_scale.has_value() && out_scale->is_cuda() &&
+                    out_scale->scalar_type() == at::kByte &&
+                    out_scale->dim() == 2 && out_scale->is_contiguous() &&
+                    out_scale->size(0) == PM && out_scale->size(1) == N / 32 &&
+                    out_scale->get_device() == out.get_device(),
+                "moe_gemm_mxfp4_mxfp8: gate_up needs out_scale [PM, N/32] "
+                "uint8 on the same GPU");
+    out_scale_p = static_cast<unsigned char*>(out_scale->data_ptr());
+  } else {
+    TORCH_CHECK(!out_scale.has_value(),
+                "moe_gemm_mxfp4_mxfp8: out_scale is for gate_up only");
+  }
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(a_q.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(a_scale.data_ptr()) % 4 == 0 &&
+                  reinterpret_cast<uintptr_t>(w_packed.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(out.data_ptr()) % 8 == 0,
+              "moe_gemm_mxfp4_mxfp8: a_q and w_packed must be 16-byte, out "
+              "8-byte and a_scale 4-byte aligned");
+  const auto dev = out.get_device();
+  TORCH_CHECK(a_q.get_device() == dev && a_scale.get_device() == dev &&
+                  w_packed.get_device() == dev &&
+                  w_scale.get_device() == dev &&
+                  sorted_ids.get_device() == dev &&
+                  expert_ids.get_device() == dev &&
+                  n_valid.get_device() == dev,
+              "moe_gemm_mxfp4_mxfp8: tensors must share one device");
+  fi::launch_moe_gemm_mxfp4_mxfp8(
+      out.data_ptr(), out_scale_p,
+      static_cast<const unsigned char*>(a_q.data_ptr()),
+      static_cast<const unsigned char*>(a_scale.data_ptr()),
+      static_cast<const unsigned char*>(w_packed.data_ptr()),
+      static_cast<const unsigned char*>(w_scale.data_ptr()),
+      sorted_ids.data_ptr<int>(), expert_ids.data_ptr<int>(),
+      n_valid.data_ptr<int>(), static_cast<int>(PM / BM), static_cast<int>(K),
+      static_cast<int>(N), gate_up, current_stream());
+}
+
 void sample_tokens(at::Tensor out, at::Tensor logits, at::Tensor temperature,
                    at::Tensor top_k, at::Tensor top_p, at::Tensor min_p,
                    at::Tensor rng) {
@@ -1283,6 +1386,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_gemm_mxfp4", &moe_gemm_mxfp4,
         "grouped W4A16 GEMM over block-aligned expert segments with MXFP4 "
         "expert weights (gate_up=true fuses the SwiGLU epilogue)");
+  m.def("moe_gemm_mxfp4_mxfp8", &moe_gemm_mxfp4_mxfp8,
+        "grouped MXFP4 x MXFP8 scaled-MFMA GEMM over 128-slot expert tiles "
+        "(gate_up=true fuses SwiGLU and the MXFP8 quantisation of its output)");
   m.def("lora_apply", &lora_apply,
         "batched multi-LoRA shrink + expand indexed by per-token slot ids "
         "(in-place on out)");

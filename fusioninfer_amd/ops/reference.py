@@ -797,3 +797,35 @@ def moe_gemm_mxfp4(out, a, w_packed, w_scale, sorted_ids, expert_ids, n_valid,
             acc = torch.nn.functional.silu(g) * u
         out[rows] = acc.to(out.dtype)
     return out
+
+
+def moe_gemm_mxfp4_mxfp8(out, a_q, a_scale, w_packed, w_scale, sorted_ids,
+                         expert_ids, n_valid, gate_up: bool, out_scale=None):
+    """Grouped MXFP4 x MXFP8 GEMM over 128-slot expert tiles: the CPU path
+    and the semantic definition of the HIP kernel. Per tile below n_valid,
+    dq(a) @ dq(W[e]).T in fp32 (a rows gathered through sorted_ids when
+    gate_up), SwiGLU in fp32, one rounding to bf16; with gate_up the bf16 row
+    is then quantised by mxfp8_quant_rows into (out, out_scale). Tiles at or
+    past n_valid are untouched. Runs on whatever device the tensors are on."""
+    block_m = 128
+    n_tiles = int(n_valid.item())
+    N = out.shape[1]
+    dq = {}
+    for mt in range(n_tiles):
+        e = int(expert_ids[mt])
+        if e not in dq:
+            dq[e] = mxfp4_dequant(w_packed[e], w_scale[e]).float()  # [NB, K]
+        rows = slice(mt * block_m, (mt + 1) * block_m)
+        src = sorted_ids[rows].long() if gate_up else rows
+        # e4m3 rows are gathered as bytes
+        a = a_q.view(torch.uint8)[src].view(torch.float8_e4m3fn)
+        acc = mxfp8_dequant(a, a_scale[src]).float() @ dq[e].t()
+        if not gate_up:
+            out[rows] = acc.to(torch.bfloat16)
+            continue
+        act = (torch.nn.functional.silu(acc[:, :N]) * acc[:, N:]).to(
+            torch.bfloat16)
+        q, s = mxfp8_quant_rows(act)
+        out.view(torch.uint8)[rows] = q.view(torch.uint8)
+        out_scale[rows] = s
+    return out if not gate_up else (out, out_scale)

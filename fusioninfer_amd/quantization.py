@@ -238,8 +238,15 @@ def convert_linear_to_mxfp4(module: nn.Module, activations: str = "bf16") -> int
     return len(layers)
 
 
-def convert_moe_experts_to_mxfp4(module: nn.Module) -> int:
+def convert_moe_experts_to_mxfp4(module: nn.Module,
+                                 activations: str = "bf16") -> int:
     """Convert the experts of every MoEMLP in a CausalLM to MXFP4 storage.
+
+    `activations` is recorded on each MoEMLP (`mlp.mxfp4_activations`) and
+    picks the path of batches routed at block_m 128: "bf16" is the grouped
+    W4A16 GEMM, "mxfp8" the grouped scaled-MFMA GEMM on MXFP8 activations
+    (ops.moe_gemm_mxfp4_mxfp8), which needs hidden_size and
+    moe_intermediate_size to be multiples of 128 like the storage itself.
 
     Each expert is quantised on its [O, I] view (the transpose of
     gate_up_t[e] / down_t[e]), one expert at a time, into the buffers
@@ -251,6 +258,10 @@ def convert_moe_experts_to_mxfp4(module: nn.Module) -> int:
     the number of converted layers."""
     from fusioninfer_amd.models.model import MoEMLP
 
+    if activations not in MXFP4_ACTIVATIONS:
+        raise ValueError(
+            f"mxfp4: MoE activations must be one of {MXFP4_ACTIVATIONS}, got "
+            f"{activations!r}")
     mlps = [m for m in module.modules() if isinstance(m, MoEMLP)]
     for m in mlps:  # reject before anything is converted
         if m.fp8 or m.mxfp4:
@@ -289,6 +300,7 @@ def convert_moe_experts_to_mxfp4(module: nn.Module) -> int:
         m.register_buffer("down_packed", dn_p, persistent=False)
         m.register_buffer("down_scale", dn_s, persistent=False)
         m.mxfp4 = True
+        m.mxfp4_activations = activations
     return len(mlps)
 
 

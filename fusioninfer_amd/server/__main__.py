@@ -61,6 +61,17 @@ def parse_args(argv=None):
                         "only on gate_up up to 256 rows and slower elsewhere "
                         "(profiles/r14_mxfp4_scaled_mfma.md). Batches up to "
                         "32 rows are identical in both")
+    p.add_argument("--mxfp4-moe-activations", choices=["bf16", "mxfp8"],
+                   default="bf16",
+                   help="with --mxfp4-moe-experts: how the experts run at "
+                        "prefill (at least 256 routed rows per local expert). "
+                        "bf16: the grouped W4A16 HIP GEMM. mxfp8: tokens are "
+                        "quantised to MXFP8 once and the grouped scaled-MFMA "
+                        "HIP GEMM reads packed weights and e4m3 activations, "
+                        "with SwiGLU and the MXFP8 quantisation of its output "
+                        "fused; activations carry e4m3 rounding "
+                        "(profiles/r15_mxfp4_moe_a8.md). Decode batches are "
+                        "identical in both")
     p.add_argument("--sampler-backend", choices=["torch", "fused"],
                    default="torch",
                    help="fused: one HIP sampling launch per step "
@@ -149,6 +160,7 @@ def build_engine_config(args):
     mc.quantization = args.quantization
     mc.mxfp4_moe_experts = args.mxfp4_moe_experts
     mc.mxfp4_activations = args.mxfp4_activations
+    mc.mxfp4_moe_activations = args.mxfp4_moe_activations
     speculative = None
     if args.speculative_config:
         from fusioninfer_amd.engine.spec_decode import SpeculativeConfig

@@ -1196,6 +1196,98 @@ def bench_mxfp4_moe(rounds=3):
                       for k, v in nbytes.items()))
 
 
+def bench_mxfp4_moe_a8(rounds=3):
+    """The prefill expert GEMM pair of Qwen3-30B-A3B (E = 128, top-8, H =
+    2048, I = 768) at block_m 128: bf16 moe_gemm, moe_gemm_mxfp4 (W4A16) and
+    moe_gemm_mxfp4_mxfp8 (scaled MFMA; its gate_up writes MXFP8) in one
+    process on the same seeded routing. Alignment is excluded; the mxfp8 pair
+    is timed both with and without its quant_mxfp8_rows(x), which the engine
+    runs once per layer. Median of 100 device-event times after 10 warm-up
+    calls; `rounds` alternating rounds, fastest..slowest round median. The
+    two mxfp4 pairs are also compared (row_rel_err of y against the W4A16
+    pair), since their activations differ by the e4m3 rounding."""
+    from fusioninfer_amd import ops
+    from fusioninfer_amd.quantization import quantize_weight_mxfp4
+
+    E, topk, H, inter = 128, 8, 2048, 768
+    dev = "cuda"
+    g = torch.Generator(device=dev).manual_seed(0)
+
+    def draw(*shape):
+        return (torch.randn(*shape, generator=g, device=dev) * 0.02).to(
+            torch.bfloat16)
+
+    w = {}
+    for name, N, K in (("gate_up", 2 * inter, H), ("down", H, inter)):
+        oi = torch.stack([draw(N, K) for _ in range(E)])  # [E, O, I]
+        q = [quantize_weight_mxfp4(oi[e]) for e in range(E)]
+        w[name] = dict(
+            bf16=ops.pack_moe_weights(oi.transpose(1, 2).contiguous()),
+            mx_p=torch.stack([p for p, _ in q]),
+            mx_s=torch.stack([s for _, s in q]),
+        )
+        del oi, q
+    gu, dn = w["gate_up"], w["down"]
+    print("\n## MXFP4 MoE experts on MXFP8 activations: gate_up + down pair at "
+          "block_m 128, Qwen3-30B-A3B shapes (median us, fastest..slowest of "
+          f"{rounds} rounds)")
+    print("| T | bf16 moe_gemm | moe_gemm_mxfp4 | moe_gemm_mxfp4_mxfp8 | "
+          "with quant(x) | bf16 fastest / a8+quant slowest | "
+          "w4a16 fastest / a8+quant slowest | y row_rel_err vs w4a16 |")
+    print("|---|---|---|---|---|---|---|---|")
+    for T in (2048, 4096, 8192):
+        x = (draw(T, H).float() * 50).to(torch.bfloat16)
+        logits = torch.randn(T, E, generator=g, device=dev)
+        _, topi = ops.moe_router_topk(logits, topk, True)
+        s, e, n, pos, PM = ops.moe_align(topi, 0, E, 128)
+        act = torch.empty(PM, inter, device=dev, dtype=torch.bfloat16)
+        y = torch.empty(PM, H, device=dev, dtype=torch.bfloat16)
+        y8 = torch.empty(PM, H, device=dev, dtype=torch.bfloat16)
+        xq, xs = ops.quant_mxfp8_rows(x)
+        aq = torch.empty(PM, inter, device=dev, dtype=torch.float8_e4m3fn)
+        asc = torch.empty(PM, inter // 32, device=dev, dtype=torch.uint8)
+
+        def bf16():
+            ops.moe_gemm(act, x, gu["bf16"], s, e, n, 128, True)
+            ops.moe_gemm(y, act, dn["bf16"], s, e, n, 128, False)
+
+        def w4a16():
+            ops.moe_gemm_mxfp4(act, x, gu["mx_p"], gu["mx_s"], s, e, n, 128,
+                               True)
+            ops.moe_gemm_mxfp4(y, act, dn["mx_p"], dn["mx_s"], s, e, n, 128,
+                               False)
+
+        def a8():
+            ops.moe_gemm_mxfp4_mxfp8(aq, xq, xs, gu["mx_p"], gu["mx_s"], s, e,
+                                     n, True, asc)
+            ops.moe_gemm_mxfp4_mxfp8(y8, aq, asc, dn["mx_p"], dn["mx_s"], s,
+                                     e, n, False)
+
+        def a8_quant():
+            ops.quant_mxfp8_rows(x, out=(xq, xs))
+            a8()
+
+        fns = (("bf16", bf16), ("w4a16", w4a16), ("a8", a8),
+               ("a8q", a8_quant))
+        meds = {name: [] for name, _ in fns}
+        for _ in range(rounds):
+            for name, fn in fns:
+                for _ in range(10):
+                    fn()
+                meds[name].append(_median(_event_times_us(fn, 100)))
+        w4a16()
+        a8()
+        rows = pos.long()
+        diff = (y8[rows].double() - y[rows].double()).norm(dim=-1)
+        err = (diff / y[rows].double().norm(dim=-1)).max().item()
+        print(f"| {T} | "
+              + " | ".join(f"{min(m):.1f}..{max(m):.1f}"
+                           for m in meds.values())
+              + f" | {min(meds['bf16']) / max(meds['a8q']):.2f}x"
+              + f" | {min(meds['w4a16']) / max(meds['a8q']):.2f}x"
+              + f" | {err:.3e} |", flush=True)
+
+
 if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "all"
     torch.manual_seed(0)
@@ -1234,3 +1326,5 @@ if __name__ == "__main__":
         bench_mxfp4()
     if which in ("mxfp4_moe", "all"):
         bench_mxfp4_moe()
+    if which in ("mxfp4_moe_a8", "all"):
+        bench_mxfp4_moe_a8()

@@ -50,7 +50,10 @@ class ModelConfig:
     # block_m 128 (T * top_k >= 256 * E_local, i.e. prefill). "bf16": the
     # grouped W4A16 GEMM. "mxfp8": x quantised to MXFP8 once per token, the
     # grouped scaled-MFMA GEMM with the SwiGLU + MXFP8 epilogue, then the
-    # scaled-MFMA down GEMM. Smaller batches (decode) are the same in both.
+    # scaled-MFMA down GEMM. "mxfp8-wide": the same pair from 8 routed rows
+    # per local expert on, at block_m 32 below 64 rows and 128 from there
+    # (models/model.py: MXFP4_MOE_WIDE_LO / _HI). Smaller batches (decode) are
+    # the same in all three.
     mxfp4_moe_activations: str = "bf16"
     # MoE (Qwen3-MoE family): num_experts 0 = dense MLP
     num_experts: int = 0

@@ -52,9 +52,10 @@ class ModelRunner:
             raise ValueError(
                 "mxfp4_activations needs quantization='mxfp4', got "
                 f"{mc.quantization!r}")
-        if mc.mxfp4_moe_activations not in ("bf16", "mxfp8"):
+        if mc.mxfp4_moe_activations not in ("bf16", "mxfp8", "mxfp8-wide"):
             raise ValueError(
-                "mxfp4_moe_activations must be 'bf16' or 'mxfp8', got "
+                "mxfp4_moe_activations must be 'bf16', 'mxfp8' or "
+                "'mxfp8-wide', got "
                 f"{mc.mxfp4_moe_activations!r}")
         if mc.mxfp4_moe_activations != "bf16" and not mc.mxfp4_moe_experts:
             raise ValueError(

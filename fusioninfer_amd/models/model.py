@@ -34,6 +34,16 @@ from fusioninfer_amd.engine.metadata import AttnMetadata
 # Read once at import, not per call: the forward is graph-captured.
 _FUSED_ROPE_CACHE = os.environ.get("FI_FUSED_ROPE_CACHE", "1") != "0"
 
+# mxfp4_moe_activations="mxfp8-wide": routed rows per local expert from which
+# the experts run the scaled-MFMA GEMM at block_m 32 (LO) and at block_m 128
+# (HI); MoEMLP._forward_mxfp4_grouped has the rule. LO == HI makes the mode
+# "mxfp8". Measured on the Qwen3-30B-A3B expert shapes
+# (profiles/r16_mxfp4_moe_a8_wide.md): block_m 32 beats the W4A16 pair from
+# 8 rows per expert, the smallest size measured, and block_m 128 beats
+# block_m 32 from 64 on.
+MXFP4_MOE_WIDE_LO = int(os.environ.get("FI_MXFP4_MOE_WIDE_LO", "8"))
+MXFP4_MOE_WIDE_HI = int(os.environ.get("FI_MXFP4_MOE_WIDE_HI", "64"))
+
 
 class Attention(nn.Module):
     def __init__(self, cfg: ModelConfig, layer_idx: int = 0):
@@ -620,14 +630,27 @@ class MoEMLP(nn.Module):
         # local expert and block_m 128 from 256 on
         # (profiles/r13_mxfp4_moe.md)
         block_m = 128 if T * self.top_k >= 256 * E_local else 16
+        a8 = block_m == 128 and self.mxfp4_activations != "bf16"
+        if self.mxfp4_activations == "mxfp8-wide":
+            # rows per local expert: the scaled-MFMA GEMM at block_m 128 from
+            # HI on and at block_m 32 from LO on; below LO the W4A16 kernel,
+            # so decode stays exact in the activations. T is a host integer:
+            # no sync, and a captured step keeps the path it was captured on
+            rows = T * self.top_k
+            if rows >= MXFP4_MOE_WIDE_HI * E_local:
+                block_m, a8 = 128, True
+            elif rows >= MXFP4_MOE_WIDE_LO * E_local:
+                block_m, a8 = ops.MOE_A8_BLOCK_M_WIDE, True
+            else:
+                block_m, a8 = 16, False
         sorted_ids, expert_ids, n_valid, pos, PM = self._moe_align(
             topi, block_m
         )
         inter = self.down_packed.shape[2] * 2
-        if block_m == 128 and self.mxfp4_activations == "mxfp8":
+        if a8:
             # x is quantised once per token and gathered by the kernel; the
             # act tensor exists only as MXFP8, written by the gate_up
-            # epilogue (block_m 128 is ops.MOE_A8_BLOCK_M)
+            # epilogue
             x_q, x_scale = ops.quant_mxfp8_rows(x)
             act_q = torch.empty(PM, inter, dtype=torch.float8_e4m3fn,
                                 device=x.device)
@@ -635,11 +658,12 @@ class MoEMLP(nn.Module):
                                     device=x.device)
             ops.moe_gemm_mxfp4_mxfp8(
                 act_q, x_q, x_scale, self.gate_up_packed, self.gate_up_scale,
-                sorted_ids, expert_ids, n_valid, True, act_scale)
+                sorted_ids, expert_ids, n_valid, True, act_scale,
+                block_m=block_m)
             y = torch.empty(PM, H, dtype=x.dtype, device=x.device)
             ops.moe_gemm_mxfp4_mxfp8(
                 y, act_q, act_scale, self.down_packed, self.down_scale,
-                sorted_ids, expert_ids, n_valid, False)
+                sorted_ids, expert_ids, n_valid, False, block_m=block_m)
         else:
             act = torch.empty(PM, inter, dtype=x.dtype, device=x.device)
             ops.moe_gemm_mxfp4(act, x, self.gate_up_packed,

@@ -899,20 +899,22 @@ def moe_gemm_mxfp4(out, a, w_packed, w_scale, sorted_ids, expert_ids, n_valid,
                               expert_ids, n_valid, block_m, gate_up)
 
 
-MOE_A8_BLOCK_M = 128  # the only m-tile of moe_gemm_mxfp4_mxfp8
+MOE_A8_BLOCK_M = 128  # the default m-tile of moe_gemm_mxfp4_mxfp8
+MOE_A8_BLOCK_M_WIDE = 32  # its narrow tile, for 32 ... 256 rows per expert
 
 
 def moe_gemm_mxfp4_mxfp8(out, a_q, a_scale, w_packed, w_scale, sorted_ids,
-                         expert_ids, n_valid, gate_up: bool, out_scale=None):
+                         expert_ids, n_valid, gate_up: bool, out_scale=None,
+                         block_m: int = MOE_A8_BLOCK_M):
     """Grouped scaled-MFMA GEMM over block-aligned expert segments (the
-    moe_gemm contract at block_m = MOE_A8_BLOCK_M = 128) with MXFP4 expert
+    moe_gemm contract at block_m = 128, the default, or 32) with MXFP4 expert
     weights and MXFP8 activations; neither operand is expanded.
 
     a_q e4m3 / a_scale uint8 as quant_mxfp8_rows returns them: x [T, K] and
     [T, K/32] with gate_up (rows gathered via sorted_ids, so x is quantised
     once per token), act [PM, K] and [PM, K/32] without. w_packed [E, NB,
     K/2] and w_scale [E, NB, K/32] are the tensors of moe_gemm_mxfp4, NB =
-    2N when gate_up. K % 128 == 0, PM a positive multiple of 128.
+    2N when gate_up. K % 128 == 0, PM a positive multiple of block_m.
 
     gate_up=False: out [PM, N] bf16, N % 16 == 0, out_scale must be None;
     returns out. A row equals mxfp4_mxfp8_linear on that row and its
@@ -924,10 +926,12 @@ def moe_gemm_mxfp4_mxfp8(out, a_q, a_scale, w_packed, w_scale, sorted_ids,
 
     Tiles at or past n_valid are not touched. Static grid, no host sync, no
     workspace, no atomics: hipGraph-capturable. A row's bits depend only on
-    its own operands. Unsupported input raises ValueError before any launch
-    (no silent fallback)."""
+    its own operands, not on block_m. Unsupported input raises ValueError
+    before any launch (no silent fallback)."""
     op = "moe_gemm_mxfp4_mxfp8"
-    BM = MOE_A8_BLOCK_M
+    if block_m not in (MOE_A8_BLOCK_M, MOE_A8_BLOCK_M_WIDE):
+        raise ValueError(f"{op}: block_m must be 128 or 32, got {block_m}")
+    BM = block_m
     want_out = torch.float8_e4m3fn if gate_up else torch.bfloat16
     if out.dtype != want_out:
         raise ValueError(
@@ -952,7 +956,7 @@ def moe_gemm_mxfp4_mxfp8(out, a_q, a_scale, w_packed, w_scale, sorted_ids,
         raise ValueError(
             f"{op}: need out [PM, N], a_q [rows, K], a_scale [rows, K/32], "
             "w_packed [E, NB, K/2], w_scale [E, NB, K/32], sorted_ids [PM], "
-            "expert_ids [PM/128] and a one-element n_valid")
+            "expert_ids [PM/block_m] and a one-element n_valid")
     tensors = [out, a_q, a_scale, w_packed, w_scale, sorted_ids, expert_ids,
                n_valid]
     PM, N = out.shape
@@ -1002,11 +1006,11 @@ def moe_gemm_mxfp4_mxfp8(out, a_q, a_scale, w_packed, w_scale, sorted_ids,
         _require_native()
         _C.moe_gemm_mxfp4_mxfp8(out, a_q, a_scale, w_packed, w_scale,
                                 sorted_ids, expert_ids, n_valid, gate_up,
-                                out_scale)
+                                out_scale, block_m)
         return (out, out_scale) if gate_up else out
     return ref.moe_gemm_mxfp4_mxfp8(out, a_q, a_scale, w_packed, w_scale,
                                     sorted_ids, expert_ids, n_valid, gate_up,
-                                    out_scale)
+                                    out_scale, block_m=block_m)
 
 
 # ---------------------------------------------------------------- sampling

@@ -1,5 +1,6 @@
 // Grouped MXFP4 x MXFP8 scaled-MFMA GEMM for MoE experts at prefill
-// (gfx950): the block_m 128 path of `--mxfp4-moe-activations mxfp8`.
+// (gfx950): the block_m 128 path of `--mxfp4-moe-activations mxfp8`, and
+// below it the block_m 32 instance of `mxfp8-wide` for mid-size batches.
 //
 //   down:    out[slot, n] = bf16( sum_k dq(a)[slot, k] * dq(W[e])[n, k] )
 //   gate_up: (out, out_scale)[slot] = mxfp8_quant_rows( bf16( swiglu(
@@ -338,11 +339,271 @@ __global__ __launch_bounds__(256, 2) void moe_mxfp4_mxfp8_gemm_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------
+// block_m 32 instance, for 32 ... 256 routed rows per expert: a weight-bound,
+// latency-bound regime (the pair reads every expert's weights and does little
+// arithmetic per byte), so the tile is narrow in M and the W prefetch deep.
+//
+// Split: 256 threads, the four waves side by side in N, sharing no W. Down:
+// a wave owns 32 slots x 64 columns (2 m-fragments x 4 n-fragments), the
+// workgroup 32 x 256. Gate_up: a wave owns 32 slots x 32 act columns (2
+// m-fragments x (2 gate + 2 up) n-fragments: one whole MX block of the act
+// row), the workgroup 32 x 128 act columns. 32 accumulator registers either
+// way, which leaves room for four named W operand sets: the fragments and
+// scale bytes of step s + 3 are requested before the MFMAs of step s, and
+// every W byte is read once per (m-tile, column tile).
+//
+// Activation panel: 32 rows x 128 B per step, one 16 B load per thread.
+// kStage steps form a group that is staged through registers into LDS (144 B
+// padded rows; one dword per row and step carries the row's 4 scale bytes)
+// behind one barrier per group, double-buffered by group; the registers hold
+// the group after next while the current one is consumed. The loop runs four
+// steps per trip without a branch; up to three remaining steps are peeled.
+//
+// Accumulation order, epilogues, bounds and the early return are those of the
+// 128-slot kernel: a (token, expert) row has the same bits in both.
+
+#ifndef FI_MOE_A8_STAGE
+#define FI_MOE_A8_STAGE 4
+#endif
+
+constexpr int kBlockM32 = 32;                       // slots of an m-tile
+constexpr int kStage = FI_MOE_A8_STAGE;             // steps per barrier
+constexpr int kPanelBytes = kBlockM32 * kRowBytes;  // one step's LDS panel
+static_assert(kStage == 1 || kStage == 2 || kStage == 4,
+              "a trip of four steps must hold whole groups");
+
+template <bool GATE_UP>
+__global__ __launch_bounds__(256, 2) void moe_mxfp4_mxfp8_gemm32_kernel(
+    void* __restrict__ out_v,               // [PM, N] bf16, or e4m3 (GATE_UP)
+    unsigned char* __restrict__ out_scale,  // GATE_UP: [PM, N/32] e8m0
+    const unsigned char* __restrict__ aq,   // GATE_UP: [T, K]; else [PM, K]
+    const unsigned char* __restrict__ asc,  // same rows, [., K/32] e8m0
+    const unsigned char* __restrict__ wq,   // [E, NB, K/2]
+    const unsigned char* __restrict__ ws,   // [E, NB, K/32]
+    const int* __restrict__ sorted_ids,     // [PM] token row per padded slot
+    const int* __restrict__ expert_ids,     // [PM/32] local expert per tile
+    const int* __restrict__ n_valid,        // device scalar: real tile count
+    const int K, const int N) {
+  const int mtile = blockIdx.x;
+  if (mtile >= *n_valid) return;
+
+  // columns of out per wave and per workgroup
+  constexpr int kWaveN = GATE_UP ? 32 : 64;
+  constexpr int kTileN = 4 * kWaveN;
+  const int tid = threadIdx.x;
+  const int lane = tid % kWaveSize;
+  const int wave = tid / kWaveSize;
+  const int r = lane & 15;
+  const int g = lane >> 4;
+  const int slot0 = mtile * kBlockM32;
+  const int wn = blockIdx.y * kTileN + kWaveN * wave;  // first column
+  const int nsteps = K / 128;
+  const int NB = GATE_UP ? 2 * N : N;
+  const int64_t wrow0 = static_cast<int64_t>(expert_ids[mtile]) * NB;
+
+  __shared__ __attribute__((aligned(16))) unsigned char
+      xl[2][kStage * kPanelBytes];
+  // [step of the group][row]; entries from 32 kStage on only give the other
+  // threads somewhere to store, so that no store is predicated
+  __shared__ u32 sl[2][256];
+
+  // panel staging: thread -> row tid / 8, 16 B chunk tid % 8 of every step of
+  // the group; scale staging: thread -> row tid % 32 of step tid / 32
+  const unsigned char* xg;
+  const unsigned char* sg;
+  const int xo = (tid >> 3) * kRowBytes + 16 * (tid & 7);
+  const int sstep = tid >> 5;
+  {
+    const int prow = slot0 + (tid >> 3);
+    const int srow = slot0 + (tid & 31);
+    xg = aq + static_cast<int64_t>(GATE_UP ? sorted_ids[prow] : prow) * K +
+         16 * (tid & 7);
+    sg = asc + static_cast<int64_t>(GATE_UP ? sorted_ids[srow] : srow) *
+                   (K / 32);
+  }
+  // W fragments and their scale bytes: lane -> row r, MX block g of the step
+  const unsigned char* wp[4];
+  const unsigned char* wsp[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    // gate_up: fragments 0, 1 are gate rows, 2, 3 the matching up rows
+    const int col = GATE_UP ? wn + 16 * (j & 1) + r : wn + 16 * j + r;
+    const int64_t n =
+        wrow0 + (GATE_UP && j >= 2 ? N : 0) + min(col, N - 1);
+    wp[j] = wq + n * (K / 2) + 16 * g;
+    wsp[j] = ws + n * (K / 32) + g;
+  }
+  // x fragment: bytes 16 g ... + 15 and 64 + 16 g ... + 15 of the row's step
+  const int xfrag = r * kRowBytes + 16 * g;
+
+  floatx4 acc[4][2];  // [n fragment][m fragment]
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int i = 0; i < 2; ++i) acc[j][i] = floatx4{0.f, 0.f, 0.f, 0.f};
+
+  // four named W operand sets: step s computes from set s & 3 while the
+  // loads of steps s + 1 ... s + 3 are in flight to the other three. Loads
+  // past the end read the last step again: in bounds, never used.
+  u32x4 wv[4][4];
+  u32 wsc[4][4];
+  u32x4 stage[kStage];
+  u32 sstage;
+  auto load_w = [&](auto P, int s) {
+    constexpr int p = decltype(P)::value;
+    const int sc = min(s, nsteps - 1);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      wv[p][j] = *reinterpret_cast<const u32x4*>(wp[j] + sc * 64);
+      wsc[p][j] = wsp[j][sc * 4];
+    }
+  };
+  // the panel group that starts at step s0: global -> registers -> LDS
+  auto load_group = [&](int s0) {
+#pragma unroll
+    for (int q = 0; q < kStage; ++q)
+      stage[q] = *reinterpret_cast<const u32x4*>(
+          xg + min(s0 + q, nsteps - 1) * 128);
+    sstage = *reinterpret_cast<const u32*>(
+        sg + min(s0 + sstep, nsteps - 1) * 4);
+  };
+  auto store_group = [&](int b) {
+#pragma unroll
+    for (int q = 0; q < kStage; ++q)
+      *reinterpret_cast<u32x4*>(&xl[b][q * kPanelBytes + xo]) = stage[q];
+    sl[b][tid] = sstage;
+  };
+  using P0 = std::integral_constant<int, 0>;
+  using P1 = std::integral_constant<int, 1>;
+  using P2 = std::integral_constant<int, 2>;
+  using P3 = std::integral_constant<int, 3>;
+  load_w(P0{}, 0);
+  load_w(P1{}, 1);
+  load_w(P2{}, 2);
+  load_group(0);
+  store_group(0);
+  load_group(kStage);
+  __syncthreads();
+  int cur = 0;  // LDS buffers of the group being consumed
+
+  // the 8 MFMAs of one step: operand set P, panel P % kStage of the group
+  auto mfmas = [&](auto P) {
+    constexpr int p = decltype(P)::value;
+    constexpr int q = p % kStage;
+    const unsigned char* buf = xl[cur] + q * kPanelBytes + xfrag;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const u32x4 lo =
+          *reinterpret_cast<const u32x4*>(buf + 16 * i * kRowBytes);
+      const u32x4 hi =
+          *reinterpret_cast<const u32x4*>(buf + 16 * i * kRowBytes + 64);
+      const intx8 xv = {static_cast<int>(lo[0]), static_cast<int>(lo[1]),
+                        static_cast<int>(lo[2]), static_cast<int>(lo[3]),
+                        static_cast<int>(hi[0]), static_cast<int>(hi[1]),
+                        static_cast<int>(hi[2]), static_cast<int>(hi[3])};
+      // byte g of the row's dword (one v_bfe_u32)
+      const u32 xsc = (sl[cur][32 * q + 16 * i + r] >> (8 * g)) & 0xffu;
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        acc[j][i] = mfma_w4a8(wv[p][j], wsc[p][j], xv, xsc, acc[j][i]);
+    }
+  };
+  // one step s of parity P = s & 3
+  auto step = [&](auto P, int s) {
+    constexpr int p = decltype(P)::value;
+    load_w(std::integral_constant<int, (p + 3) & 3>{}, s + 3);
+    FI_SCHED_FENCE();  // the loads are issued before the MFMAs ...
+    mfmas(P);
+    FI_SCHED_FENCE();  // ... and waited for only after them
+    if constexpr ((p + 1) % kStage == 0) {
+      // the group ends: the next one goes to the buffers last read one group
+      // ago, before that group's barrier, and the one after it is requested
+      store_group(cur ^ 1);
+      load_group(s + 1 + kStage);
+      __syncthreads();
+      cur ^= 1;
+    }
+  };
+  int s = 0;
+  for (; s + 3 < nsteps; s += 4) {
+    step(P0{}, s);
+    step(P1{}, s + 1);
+    step(P2{}, s + 2);
+    step(P3{}, s + 3);
+  }
+  // peeled remainder: same steps, their extra loads clamped to the last one
+  const int rem = nsteps - s;
+  if (rem >= 1) step(P0{}, s);
+  if (rem >= 2) step(P1{}, s + 1);
+  if (rem == 3) step(P2{}, s + 2);
+
+  // lane -> slot r of each m fragment, columns 4 g ... + 3 of each n
+  // fragment
+  if constexpr (!GATE_UP) {
+    u16* out = static_cast<u16*>(out_v);
+    // N % 16 == 0, so a fragment is stored whole or not at all
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int n = wn + 16 * j + 4 * g;
+      if (n < N) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          const int64_t slot = slot0 + 16 * i + r;
+          bf16x4 o;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) o.h[e] = f32_to_bf16(acc[j][i][e]);
+          *reinterpret_cast<bf16x4*>(out + slot * N + n) = o;
+        }
+      }
+    }
+  } else {
+    unsigned char* out = static_cast<unsigned char*>(out_v);
+    // N % 32 == 0, so a wave's MX block of act columns is whole or absent
+    // (wave-uniform; every barrier is behind us)
+    if (wn < N) {
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int64_t slot = slot0 + 16 * i + r;
+        float v[2][4];
+        float amax = 0.f;
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            v[j][e] = bf16_to_f32(
+                f32_to_bf16(swiglu(acc[j][i][e], acc[j + 2][i][e])));
+            amax = fmaxf(amax, fabsf(v[j][e]));
+          }
+        amax = fmaxf(amax, __shfl_xor(amax, 16, 64));
+        amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
+        // quant_mxfp8_rows' rule, as in the 128-slot kernel
+        int sb = static_cast<int>((__float_as_uint(amax) >> 23) & 0xff) - 8;
+        sb = min(max(sb, 8), 247);
+        if (amax == 0.f) sb = 127;
+        const float inv = __uint_as_float(static_cast<u32>(254 - sb) << 23);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          // the convert gives NaN past 448 instead of saturating: clamp first
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            v[j][e] = fminf(fmaxf(v[j][e] * inv, -448.f), 448.f);
+          *reinterpret_cast<u32*>(out + slot * N + wn + 16 * j + 4 * g) =
+              pack_fp8x4(v[j]);
+        }
+        if (g == 0)
+          out_scale[slot * (N / 32) + wn / 32] =
+              static_cast<unsigned char>(sb);
+      }
+    }
+  }
+}
+
 }  // namespace
 
 // K % 128 == 0, N % 16 == 0 (N % 32 == 0 with gate_up), max_mtiles tiles of
-// 128 slots (checked by the binding). The grid is static and tiles at or
-// past *n_valid leave at once.
+// block_m = 128 or 32 slots (checked by the binding). The grid is static and
+// tiles at or past *n_valid leave at once.
 void launch_moe_gemm_mxfp4_mxfp8(void* out, unsigned char* out_scale,
                                  const unsigned char* aq,
                                  const unsigned char* asc,
@@ -350,7 +611,21 @@ void launch_moe_gemm_mxfp4_mxfp8(void* out, unsigned char* out_scale,
                                  const unsigned char* ws,
                                  const int* sorted_ids, const int* expert_ids,
                                  const int* n_valid, int max_mtiles, int K,
-                                 int N, bool gate_up, hipStream_t stream) {
+                                 int N, bool gate_up, int block_m,
+                                 hipStream_t stream) {
+  if (block_m == kBlockM32) {
+    if (gate_up)
+      moe_mxfp4_mxfp8_gemm32_kernel<true>
+          <<<dim3(max_mtiles, ceil_div(N, 128)), 256, 0, stream>>>(
+              out, out_scale, aq, asc, wq, ws, sorted_ids, expert_ids,
+              n_valid, K, N);
+    else
+      moe_mxfp4_mxfp8_gemm32_kernel<false>
+          <<<dim3(max_mtiles, ceil_div(N, 256)), 256, 0, stream>>>(
+              out, out_scale, aq, asc, wq, ws, sorted_ids, expert_ids,
+              n_valid, K, N);
+    return;
+  }
   if (gate_up)
     moe_mxfp4_mxfp8_gemm_kernel<true>
         <<<dim3(max_mtiles, ceil_div(N, 64)), 256, 0, stream>>>(

@@ -70,7 +70,8 @@ void launch_moe_gemm_mxfp4(u16*, const u16*, const unsigned char*,
 void launch_moe_gemm_mxfp4_mxfp8(void*, unsigned char*, const unsigned char*,
                                  const unsigned char*, const unsigned char*,
                                  const unsigned char*, const int*, const int*,
-                                 const int*, int, int, int, bool, hipStream_t);
+                                 const int*, int, int, int, bool, int,
+                                 hipStream_t);
 void launch_sample_tokens(int64_t*, const float*, const float*, const int*,
                           const float*, const float*, const int64_t*, int,
                           int, hipStream_t);
@@ -970,7 +971,8 @@ void moe_gemm_mxfp4(at::Tensor out, at::Tensor a, at::Tensor w_packed,
       gate_up, current_stream());
 }
 
-// grouped scaled-MFMA GEMM, m-tiles of 128 slots: a_q e4m3 and a_scale e8m0
+// grouped scaled-MFMA GEMM, m-tiles of block_m = 128 or 32 slots: a_q e4m3 and
+// a_scale e8m0
 // are x [T, .] (gate_up, gathered via sorted_ids) or act [PM, .]; weights as
 // moe_gemm_mxfp4. gate_up writes MXFP8 (out e4m3 [PM, N], out_scale [PM,
 // N/32]), down writes bf16 and takes no out_scale
@@ -978,8 +980,11 @@ void moe_gemm_mxfp4_mxfp8(at::Tensor out, at::Tensor a_q, at::Tensor a_scale,
                           at::Tensor w_packed, at::Tensor w_scale,
                           at::Tensor sorted_ids, at::Tensor expert_ids,
                           at::Tensor n_valid, bool gate_up,
-                          c10::optional<at::Tensor> out_scale) {
-  constexpr int64_t BM = 128;
+                          c10::optional<at::Tensor> out_scale,
+                          int64_t block_m) {
+  TORCH_CHECK(block_m == 128 || block_m == 32,
+              "moe_gemm_mxfp4_mxfp8: block_m must be 128 or 32");
+  const int64_t BM = block_m;
   TORCH_CHECK(out.is_cuda() && out.dim() == 2 && out.is_contiguous() &&
                   out.scalar_type() ==
                       (gate_up ? at::kFloat8_e4m3fn : at::kBFloat16),
@@ -1018,7 +1023,8 @@ void moe_gemm_mxfp4_mxfp8(at::Tensor out, at::Tensor a_q, at::Tensor a_scale,
               "moe_gemm_mxfp4_mxfp8: need K % 128 == 0 and N % 16 == 0 "
               "(N % 32 == 0 with gate_up)");
   TORCH_CHECK(PM >= BM && PM % BM == 0 && PM < (1LL << 31),
-              "moe_gemm_mxfp4_mxfp8: padded rows must be a multiple of 128");
+              "moe_gemm_mxfp4_mxfp8: padded rows must be a positive multiple "
+              "of block_m");
   TORCH_CHECK(w_packed.size(0) >= 1 && w_packed.size(1) == NB &&
                   w_packed.size(2) == K / 2 &&
                   w_scale.size(0) == w_packed.size(0) &&
@@ -1066,7 +1072,7 @@ void moe_gemm_mxfp4_mxfp8(at::Tensor out, at::Tensor a_q, at::Tensor a_scale,
       static_cast<const unsigned char*>(w_scale.data_ptr()),
       sorted_ids.data_ptr<int>(), expert_ids.data_ptr<int>(),
       n_valid.data_ptr<int>(), static_cast<int>(PM / BM), static_cast<int>(K),
-      static_cast<int>(N), gate_up, current_stream());
+      static_cast<int>(N), gate_up, static_cast<int>(BM), current_stream());
 }
 
 void sample_tokens(at::Tensor out, at::Tensor logits, at::Tensor temperature,
@@ -1387,7 +1393,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "grouped W4A16 GEMM over block-aligned expert segments with MXFP4 "
         "expert weights (gate_up=true fuses the SwiGLU epilogue)");
   m.def("moe_gemm_mxfp4_mxfp8", &moe_gemm_mxfp4_mxfp8,
-        "grouped MXFP4 x MXFP8 scaled-MFMA GEMM over 128-slot expert tiles "
+        "grouped MXFP4 x MXFP8 scaled-MFMA GEMM over 128- or 32-slot expert tiles "
         "(gate_up=true fuses SwiGLU and the MXFP8 quantisation of its output)");
   m.def("lora_apply", &lora_apply,
         "batched multi-LoRA shrink + expand indexed by per-token slot ids "

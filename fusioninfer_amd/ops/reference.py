@@ -800,14 +800,14 @@ def moe_gemm_mxfp4(out, a, w_packed, w_scale, sorted_ids, expert_ids, n_valid,
 
 
 def moe_gemm_mxfp4_mxfp8(out, a_q, a_scale, w_packed, w_scale, sorted_ids,
-                         expert_ids, n_valid, gate_up: bool, out_scale=None):
-    """Grouped MXFP4 x MXFP8 GEMM over 128-slot expert tiles: the CPU path
+                         expert_ids, n_valid, gate_up: bool, out_scale=None,
+                         block_m: int = 128):
+    """Grouped MXFP4 x MXFP8 GEMM over block_m-slot expert tiles: the CPU path
     and the semantic definition of the HIP kernel. Per tile below n_valid,
     dq(a) @ dq(W[e]).T in fp32 (a rows gathered through sorted_ids when
     gate_up), SwiGLU in fp32, one rounding to bf16; with gate_up the bf16 row
     is then quantised by mxfp8_quant_rows into (out, out_scale). Tiles at or
     past n_valid are untouched. Runs on whatever device the tensors are on."""
-    block_m = 128
     n_tiles = int(n_valid.item())
     N = out.shape[1]
     dq = {}

@@ -189,6 +189,10 @@ class _Mxfp4Scratch:
 
 
 MXFP4_ACTIVATIONS = ("bf16", "mxfp8")
+# the experts also take "mxfp8-wide": the scaled-MFMA GEMM from
+# MXFP4_MOE_WIDE_LO routed rows per expert on, at block_m 32 below
+# MXFP4_MOE_WIDE_HI (models/model.py)
+MXFP4_MOE_ACTIVATIONS = MXFP4_ACTIVATIONS + ("mxfp8-wide",)
 
 
 def convert_linear_to_mxfp4(module: nn.Module, activations: str = "bf16") -> int:
@@ -247,6 +251,8 @@ def convert_moe_experts_to_mxfp4(module: nn.Module,
     W4A16 GEMM, "mxfp8" the grouped scaled-MFMA GEMM on MXFP8 activations
     (ops.moe_gemm_mxfp4_mxfp8), which needs hidden_size and
     moe_intermediate_size to be multiples of 128 like the storage itself.
+    "mxfp8-wide" runs that GEMM on mid-size batches too, at block_m 32
+    (MoEMLP._forward_mxfp4_grouped has the rule).
 
     Each expert is quantised on its [O, I] view (the transpose of
     gate_up_t[e] / down_t[e]), one expert at a time, into the buffers
@@ -258,9 +264,10 @@ def convert_moe_experts_to_mxfp4(module: nn.Module,
     the number of converted layers."""
     from fusioninfer_amd.models.model import MoEMLP
 
-    if activations not in MXFP4_ACTIVATIONS:
+    if activations not in MXFP4_MOE_ACTIVATIONS:
         raise ValueError(
-            f"mxfp4: MoE activations must be one of {MXFP4_ACTIVATIONS}, got "
+            "mxfp4: MoE activations must be one of "
+            f"{MXFP4_MOE_ACTIVATIONS}, got "
             f"{activations!r}")
     mlps = [m for m in module.modules() if isinstance(m, MoEMLP)]
     for m in mlps:  # reject before anything is converted

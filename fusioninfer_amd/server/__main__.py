@@ -61,8 +61,8 @@ def parse_args(argv=None):
                         "only on gate_up up to 256 rows and slower elsewhere "
                         "(profiles/r14_mxfp4_scaled_mfma.md). Batches up to "
                         "32 rows are identical in both")
-    p.add_argument("--mxfp4-moe-activations", choices=["bf16", "mxfp8"],
-                   default="bf16",
+    p.add_argument("--mxfp4-moe-activations",
+                   choices=["bf16", "mxfp8", "mxfp8-wide"], default="bf16",
                    help="with --mxfp4-moe-experts: how the experts run at "
                         "prefill (at least 256 routed rows per local expert). "
                         "bf16: the grouped W4A16 HIP GEMM. mxfp8: tokens are "
@@ -70,8 +70,12 @@ def parse_args(argv=None):
                         "HIP GEMM reads packed weights and e4m3 activations, "
                         "with SwiGLU and the MXFP8 quantisation of its output "
                         "fused; activations carry e4m3 rounding "
-                        "(profiles/r15_mxfp4_moe_a8.md). Decode batches are "
-                        "identical in both")
+                        "(profiles/r15_mxfp4_moe_a8.md). mxfp8-wide: mxfp8, "
+                        "and batches from FI_MXFP4_MOE_WIDE_LO (8) routed "
+                        "rows per local expert run the same GEMM at block_m "
+                        "32, from FI_MXFP4_MOE_WIDE_HI (64) at block_m 128 "
+                        "(profiles/r16_mxfp4_moe_a8_wide.md). Batches below "
+                        "LO (decode) are identical in all three")
     p.add_argument("--sampler-backend", choices=["torch", "fused"],
                    default="torch",
                    help="fused: one HIP sampling launch per step "

@@ -1288,6 +1288,104 @@ def bench_mxfp4_moe_a8(rounds=3):
               + f" | {err:.3e} |", flush=True)
 
 
+def bench_mxfp4_moe_a8_wide(rounds=3):
+    """The expert GEMM pair of Qwen3-30B-A3B (E = 128, top-8, H = 2048, I =
+    768) at 8 to 256 routed rows per expert: bf16 moe_gemm at its own rule's
+    block_m, moe_gemm_mxfp4 (W4A16) at block_m 16, and moe_gemm_mxfp4_mxfp8
+    at block_m 32 and 128 with quant_mxfp8_rows(x) inside the timed call.
+    One process, the same seeded routing; alignment is excluded. Median of
+    100 device-event times after 10 warm-up calls; `rounds` alternating
+    rounds, fastest..slowest round median. y of the block_m 32 pair is
+    compared with the W4A16 pair's (row_rel_err: the price of e4m3
+    activations) and with the block_m 128 pair's (must be bit-equal)."""
+    from fusioninfer_amd import ops
+    from fusioninfer_amd.quantization import quantize_weight_mxfp4
+
+    E, topk, H, inter = 128, 8, 2048, 768
+    dev = "cuda"
+    g = torch.Generator(device=dev).manual_seed(0)
+
+    def draw(*shape):
+        return (torch.randn(*shape, generator=g, device=dev) * 0.02).to(
+            torch.bfloat16)
+
+    w = {}
+    for name, N, K in (("gate_up", 2 * inter, H), ("down", H, inter)):
+        oi = torch.stack([draw(N, K) for _ in range(E)])  # [E, O, I]
+        q = [quantize_weight_mxfp4(oi[e]) for e in range(E)]
+        w[name] = dict(
+            bf16=ops.pack_moe_weights(oi.transpose(1, 2).contiguous()),
+            mx_p=torch.stack([p for p, _ in q]),
+            mx_s=torch.stack([s for _, s in q]),
+        )
+        del oi, q
+    gu, dn = w["gate_up"], w["down"]
+    print("\n## MXFP4 MoE experts on MXFP8 activations at block_m 32: gate_up "
+          "+ down pair, Qwen3-30B-A3B shapes (median us, fastest..slowest of "
+          f"{rounds} rounds; a8 includes quant(x))")
+    print("| T | rows/expert | bf16 moe_gemm | w4a16 block_m 16 | a8 block_m "
+          "32 | a8 block_m 128 | y row_rel_err vs w4a16 | 32 == 128 |")
+    print("|---|---|---|---|---|---|---|---|")
+    for T in (128, 256, 512, 1024, 2048, 4096):
+        x = (draw(T, H).float() * 50).to(torch.bfloat16)
+        logits = torch.randn(T, E, generator=g, device=dev)
+        _, topi = ops.moe_router_topk(logits, topk, True)
+        bm_bf16 = 128 if T * topk >= 64 * E else 16
+        xq, xs = ops.quant_mxfp8_rows(x)
+        al, buf = {}, {}
+        for bm in {16, 32, 128, bm_bf16}:
+            al[bm] = ops.moe_align(topi, 0, E, bm)
+            PM = al[bm][4]
+            buf[bm] = dict(
+                act=torch.empty(PM, inter, device=dev, dtype=torch.bfloat16),
+                y=torch.empty(PM, H, device=dev, dtype=torch.bfloat16),
+                aq=torch.empty(PM, inter, device=dev,
+                               dtype=torch.float8_e4m3fn),
+                asc=torch.empty(PM, inter // 32, device=dev,
+                                dtype=torch.uint8))
+
+        def bf16():
+            (s, e, n, _, _), b = al[bm_bf16], buf[bm_bf16]
+            ops.moe_gemm(b["act"], x, gu["bf16"], s, e, n, bm_bf16, True)
+            ops.moe_gemm(b["y"], b["act"], dn["bf16"], s, e, n, bm_bf16,
+                         False)
+
+        def w4a16():
+            (s, e, n, _, _), b = al[16], buf[16]
+            ops.moe_gemm_mxfp4(b["act"], x, gu["mx_p"], gu["mx_s"], s, e, n,
+                               16, True)
+            ops.moe_gemm_mxfp4(b["y"], b["act"], dn["mx_p"], dn["mx_s"], s, e,
+                               n, 16, False)
+
+        def a8(bm):
+            (s, e, n, _, _), b = al[bm], buf[bm]
+            ops.quant_mxfp8_rows(x, out=(xq, xs))
+            ops.moe_gemm_mxfp4_mxfp8(b["aq"], xq, xs, gu["mx_p"], gu["mx_s"],
+                                     s, e, n, True, b["asc"], block_m=bm)
+            ops.moe_gemm_mxfp4_mxfp8(b["y"], b["aq"], b["asc"], dn["mx_p"],
+                                     dn["mx_s"], s, e, n, False, block_m=bm)
+
+        fns = (("bf16", bf16), ("w4a16", w4a16), ("a8_32", lambda: a8(32)),
+               ("a8_128", lambda: a8(128)))
+        meds = {name: [] for name, _ in fns}
+        for _ in range(rounds):
+            for name, fn in fns:
+                for _ in range(10):
+                    fn()
+                meds[name].append(_median(_event_times_us(fn, 100)))
+        w4a16()
+        a8(32)
+        a8(128)
+        y16 = buf[16]["y"][al[16][3].long()].double()
+        y32 = buf[32]["y"][al[32][3].long()]
+        err = ((y32.double() - y16).norm(dim=-1) / y16.norm(dim=-1)).max()
+        same = torch.equal(y32, buf[128]["y"][al[128][3].long()])
+        print(f"| {T} | {T * topk // E} | "
+              + " | ".join(f"{min(m):.1f}..{max(m):.1f}"
+                           for m in meds.values())
+              + f" | {err.item():.3e} | {same} |", flush=True)
+
+
 if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "all"
     torch.manual_seed(0)
@@ -1328,3 +1426,5 @@ if __name__ == "__main__":
         bench_mxfp4_moe()
     if which in ("mxfp4_moe_a8", "all"):
         bench_mxfp4_moe_a8()
+    if which in ("mxfp4_moe_a8_wide", "all"):
+        bench_mxfp4_moe_a8_wide()

@@ -25,6 +25,10 @@ class AttnMetadata:
     tile_rows: int = 0                           # rows per tile (0 = default)
     prefill_block_tables: Optional[torch.Tensor] = None  # [P, max_blocks]
     prefill_seq_lens_k: Optional[torch.Tensor] = None    # [P] total ctx
+    # > 0: every prefill chunk has at most this many rows (and at most
+    # ops.SHORTQ_MAX_ROWS) and attention runs paged_attention_shortq; the
+    # tile table is then not built
+    prefill_short_q: int = 0
     # decode segment
     block_tables: Optional[torch.Tensor] = None  # [Dq, max_blocks] int32
     seq_lens: Optional[torch.Tensor] = None      # [Dq] int32 (ctx incl. current)

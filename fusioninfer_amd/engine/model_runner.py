@@ -120,6 +120,13 @@ class ModelRunner:
                         self.model, mc.mxfp4_moe_activations) > 0
         if mc.quantization not in (None, "fp8", "mxfp4"):
             raise ValueError(f"unknown quantization {mc.quantization!r}")
+        spec = getattr(cfg, "speculative", None)
+        verify_attention = spec.verify_attention if spec else "prefill"
+        if verify_attention not in ("prefill", "shortq"):
+            raise ValueError(
+                "speculative verify_attention must be 'prefill' or 'shortq', "
+                f"got {verify_attention!r}")
+        self.shortq_verify = verify_attention == "shortq"
         if self.is_cuda and os.environ.get(
                 "FI_MOE_KEEP_UNPACKED", "0") != "1":
             # weights are final: keep only the MFMA-packed expert layout
@@ -343,17 +350,29 @@ class ModelRunner:
         with torch.no_grad():
             return self._forward_and_logits(ids, meta, logits_idx)
 
+    def _prefill_attn_plan(self, payload):
+        """(tile_seq, tile_row0, tile_rows, prefill_short_q) of a payload's
+        prefill segment: the tile table of prefill_attention_paged, or no
+        table and the longest chunk when verify_attention is "shortq" and
+        every chunk fits paged_attention_shortq."""
+        new_lens = payload["new_lens"]
+        if (self.shortq_verify and new_lens
+                and max(new_lens) <= ops_mod.SHORTQ_MAX_ROWS):
+            return None, None, 0, max(new_lens)
+        tile_rows = ops_mod.prefill_tile_rows(new_lens)
+        tile_seq, tile_row0 = ops_mod.build_prefill_tiles(
+            new_lens, device=self.device, rows=tile_rows,
+            ctx_starts=[
+                t - n for t, n in zip(payload["total_lens"], new_lens)
+            ],
+        )
+        return tile_seq, tile_row0, tile_rows, 0
+
     def _prefill_inputs(self, payload):
         dev = self.device
         cu = payload["cu"]
-        tile_rows = ops_mod.prefill_tile_rows(payload["new_lens"])
-        tile_seq, tile_row0 = ops_mod.build_prefill_tiles(
-            payload["new_lens"], device=dev, rows=tile_rows,
-            ctx_starts=[
-                t - n
-                for t, n in zip(payload["total_lens"], payload["new_lens"])
-            ],
-        )
+        tile_seq, tile_row0, tile_rows, short_q = self._prefill_attn_plan(
+            payload)
         meta = AttnMetadata(
             num_prefill_tokens=cu[-1],
             num_decode_tokens=0,
@@ -367,6 +386,7 @@ class ModelRunner:
             tile_seq=tile_seq,
             tile_rows=tile_rows,
             tile_row0=tile_row0,
+            prefill_short_q=short_q,
             prefill_block_tables=torch.tensor(
                 payload["bt"], dtype=torch.int32, device=dev
             ),
@@ -665,14 +685,8 @@ class ModelRunner:
         cu = payload["cu"]
         np_ = cu[-1]
         nd = len(d["ids"])
-        tile_rows = ops_mod.prefill_tile_rows(payload["new_lens"])
-        tile_seq, tile_row0 = ops_mod.build_prefill_tiles(
-            payload["new_lens"], device=dev, rows=tile_rows,
-            ctx_starts=[
-                t - n
-                for t, n in zip(payload["total_lens"], payload["new_lens"])
-            ],
-        )
+        tile_seq, tile_row0, tile_rows, short_q = self._prefill_attn_plan(
+            payload)
         max_blocks = max(len(b) for b in d["bt"])
         dbt_np = np.zeros((nd, max_blocks), dtype=np.int32)
         for i, ids in enumerate(d["bt"]):
@@ -692,6 +706,7 @@ class ModelRunner:
             tile_seq=tile_seq,
             tile_rows=tile_rows,
             tile_row0=tile_row0,
+            prefill_short_q=short_q,
             prefill_block_tables=torch.tensor(
                 payload["bt"], dtype=torch.int32, device=dev
             ),

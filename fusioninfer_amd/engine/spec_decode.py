@@ -71,6 +71,10 @@ class SpeculativeConfig:
     # requests draftable. False keeps drafting to what seq_is_draftable
     # admits. No effect with the torch backend.
     sampled_verify: bool = True
+    # attention op of the verify step (and of any prefill-kind step whose
+    # chunks are all at most ops.SHORTQ_MAX_ROWS rows): "prefill" keeps
+    # prefill_attention_paged, "shortq" takes paged_attention_shortq
+    verify_attention: str = "prefill"
 
 
 def seq_is_draftable(seq: Sequence) -> bool:

@@ -136,7 +136,24 @@ class Attention(nn.Module):
         if _FUSED_ROPE_CACHE:
             out_p = out[:np_].view(np_, self.num_heads, self.head_dim)
             out_d = out[np_:].view(nd, self.num_heads, self.head_dim)
-        if np_ > 0:
+        if np_ > 0 and meta.prefill_short_q:
+            # every chunk is a few rows (a speculative verify step): the
+            # short-query kernel splits the context and shares K/V reads
+            # across the GQA group
+            o = ops.paged_attention_shortq(
+                q[:np_].view(np_, self.num_heads, self.head_dim),
+                k_cache,
+                v_cache,
+                meta.prefill_block_tables,
+                meta.cu_seqlens,
+                meta.prefill_seq_lens_k,
+                scale,
+                max_q=meta.prefill_short_q,
+                out=out_p,
+            )
+            if out_p is None:
+                out[:np_] = o.view(np_, self.q_size)
+        elif np_ > 0:
             # context attention over the paged cache (the new tokens' K/V
             # were just written above); cached prefixes are never recomputed
             o = ops.prefill_attention_paged(

@@ -457,6 +457,90 @@ def prefill_attention_paged(
     return res if out is None else out.copy_(res)
 
 
+SHORTQ_MAX_ROWS = 32  # q rows per sequence (kernel contract)
+
+
+def paged_attention_shortq(
+    q: torch.Tensor,             # [T, Hq, D] new tokens only
+    k_cache: torch.Tensor,       # [B, Hk, 16, D] bf16 or e4m3
+    v_cache: torch.Tensor,
+    block_tables: torch.Tensor,  # [S, max_blocks] int32
+    cu_seqlens_q: torch.Tensor,  # [S+1] int32 over new tokens
+    seq_lens_k: torch.Tensor,    # [S] int32 total context length
+    scale: Optional[float] = None,
+    max_q: Optional[int] = None,
+    out: Optional[torch.Tensor] = None,  # [T, Hq, D] contiguous, written
+) -> torch.Tensor:
+    """prefill_attention_paged for sequences of at most SHORTQ_MAX_ROWS new
+    rows each (speculative verify chunks): the context is split into
+    512-token partitions and every K/V element is read once per GQA group.
+    `max_q` is a host-known upper bound on the rows of any sequence; the
+    launch grid depends on shapes and max_q only. A sequence with no rows
+    is skipped."""
+    op = "paged_attention_shortq"
+    if max_q is None:
+        max_q = SHORTQ_MAX_ROWS
+    if not 1 <= max_q <= SHORTQ_MAX_ROWS:
+        raise ValueError(
+            f"{op}: max_q must be in [1, {SHORTQ_MAX_ROWS}], got {max_q}")
+    if q.dim() != 3 or q.dtype != torch.bfloat16:
+        raise ValueError(f"{op}: q must be a [T, Hq, D] bf16 tensor")
+    T, Hq, D = q.shape
+    if (k_cache.dtype not in (torch.bfloat16, torch.float8_e4m3fn)
+            or v_cache.dtype != k_cache.dtype or k_cache.dim() != 4
+            or v_cache.shape != k_cache.shape):
+        raise ValueError(
+            f"{op}: k_cache and v_cache must be [B, Hk, 16, D] tensors of "
+            "one dtype, bf16 or float8_e4m3fn")
+    if D not in (64, 128) or k_cache.shape[3] != D:
+        raise ValueError(f"{op}: head_dim must be 64 or 128 in q and the "
+                         f"cache, got {D} and {k_cache.shape[3]}")
+    if k_cache.shape[2] != 16:
+        raise ValueError(f"{op}: cache block_size must be 16")
+    Hk = k_cache.shape[1]
+    if Hk == 0 or Hq % Hk or not 1 <= Hq // Hk <= 8:
+        raise ValueError(
+            f"{op}: need Hq == Hk * G with 1 <= G <= 8, got Hq={Hq} Hk={Hk}")
+    for name, t in (("block_tables", block_tables),
+                    ("cu_seqlens_q", cu_seqlens_q),
+                    ("seq_lens_k", seq_lens_k)):
+        if t.dtype != torch.int32 or t.device != q.device:
+            raise ValueError(f"{op}: {name} must be int32 on {q.device}")
+    S = seq_lens_k.numel()
+    if (block_tables.dim() != 2 or block_tables.shape[0] != S
+            or cu_seqlens_q.numel() != S + 1):
+        raise ValueError(f"{op}: need block_tables [S, W], cu_seqlens_q "
+                         "[S+1] and seq_lens_k [S]")
+    if T > S * max_q:
+        raise ValueError(f"{op}: T={T} rows exceed S * max_q = {S * max_q}")
+    if scale is None:
+        scale = 1.0 / math.sqrt(D)
+    if out is not None:
+        _check_attn_out(out, q)
+    if q.is_cuda:
+        _require_native()
+        if out is None:
+            out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+        # partitions from the block-table width, as in paged_attention_decode
+        num_parts = max(
+            -(-int(block_tables.shape[1]) * 16 // DECODE_PARTITION_TOKENS), 1)
+        ml_ws = acc_ws = None
+        if num_parts > 1:
+            ml_ws = torch.empty(
+                (T, Hq, num_parts, 2), dtype=torch.float32, device=q.device)
+            acc_ws = torch.empty(
+                (T, Hq, num_parts, D), dtype=torch.float32, device=q.device)
+        _C.paged_attention_shortq(
+            out, q, k_cache, v_cache, block_tables.contiguous(),
+            cu_seqlens_q.contiguous(), seq_lens_k.contiguous(),
+            ml_ws, acc_ws, num_parts, max_q, scale)
+        return out
+    res = ref.prefill_attention_paged(
+        q, k_cache, v_cache, block_tables, cu_seqlens_q, seq_lens_k, scale
+    )
+    return res if out is None else out.copy_(res)
+
+
 # ---------------------------------------------------------------- MoE
 
 def pack_moe_weights(w: torch.Tensor) -> torch.Tensor:

@@ -26,6 +26,7 @@ SOURCES = [
     "cache.hip",
     "paged_attention.hip",
     "prefill_attention.hip",
+    "shortq_attention.hip",
     "moe_gemm.hip",
     "lora.hip",
     "sampling.hip",

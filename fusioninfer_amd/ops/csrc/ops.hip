@@ -38,6 +38,10 @@ void launch_prefill_attn(u16*, const u16*, const void*, const void*,
                          const int*, const int*, const int*, const int*,
                          const int*, int, int, int64_t, int64_t, int64_t, int,
                          int, int, float, bool, int, bool, hipStream_t);
+void launch_shortq_attn(u16*, float*, float*, const u16*, const void*,
+                        const void*, const int*, const int*, const int*, int,
+                        int, int64_t, int, int, int, int, int, int, float,
+                        bool, hipStream_t);
 void launch_moe_gemm(u16*, const u16*, const u16*, const int*, const int*,
                      const int*, int, int, int, int, bool, hipStream_t);
 void launch_moe_gemm_fp8(u16*, const unsigned char*, const float*,
@@ -578,6 +582,86 @@ void prefill_attention_paged(at::Tensor out, at::Tensor q, at::Tensor k_cache,
       q.stride(0), 0, 0, num_q_heads, num_kv_heads, head_dim,
       static_cast<float>(scale), fp8,
       static_cast<int>(tile_rows / 32), heads_adjacent, current_stream());
+}
+
+// a few q rows per sequence (at most 32) against the paged cache; see
+// shortq_attention.hip. num_parts and the workspaces follow
+// paged_attention_decode, with T rows in place of S.
+void paged_attention_shortq(at::Tensor out, at::Tensor q, at::Tensor k_cache,
+                            at::Tensor v_cache, at::Tensor block_tables,
+                            at::Tensor cu_seqlens_q, at::Tensor seq_lens_k,
+                            c10::optional<at::Tensor> ml_ws,
+                            c10::optional<at::Tensor> acc_ws,
+                            int64_t num_parts, int64_t max_q, double scale) {
+  const char* op = "paged_attention_shortq";
+  CHECK_BF16_CUDA(out);
+  CHECK_BF16_CUDA(q);
+  const bool fp8 = cache_is_fp8(k_cache);
+  TORCH_CHECK(v_cache.scalar_type() == k_cache.scalar_type() &&
+                  k_cache.dim() == 4 && v_cache.sizes() == k_cache.sizes() &&
+                  k_cache.is_contiguous() && v_cache.is_contiguous() &&
+                  k_cache.device() == q.device() &&
+                  v_cache.device() == q.device(),
+              op, ": k_cache and v_cache must be contiguous [B, Hk, 16, D] "
+              "tensors of one dtype on q's device");
+  for (const at::Tensor* t : {&block_tables, &cu_seqlens_q, &seq_lens_k})
+    TORCH_CHECK(t->scalar_type() == at::kInt && t->is_contiguous() &&
+                    t->device() == q.device(),
+                op, ": index tensors must be contiguous int32 on q's device");
+  TORCH_CHECK(q.dim() == 3, op, ": q must be [T, Hq, D]");
+  const int64_t total_rows = q.size(0);
+  const int64_t num_heads = q.size(1);
+  const int64_t head_dim = q.size(2);
+  const int64_t num_kv_heads = k_cache.size(1);
+  const int64_t num_seqs = seq_lens_k.numel();
+  check_attn_head_dim(op, head_dim);
+  TORCH_CHECK(k_cache.size(3) == head_dim, op, ": cache head_dim mismatch");
+  TORCH_CHECK(k_cache.size(2) == 16, op, ": cache block_size must be 16");
+  const int64_t g = num_kv_heads > 0 ? num_heads / num_kv_heads : 0;
+  TORCH_CHECK(g >= 1 && g <= 8 && g * num_kv_heads == num_heads, op,
+              ": need Hq == Hk * G with 1 <= G <= 8, got Hq=", num_heads,
+              " Hk=", num_kv_heads);
+  TORCH_CHECK(max_q >= 1 && max_q <= 32, op, ": max_q must be in [1, 32]");
+  TORCH_CHECK(block_tables.dim() == 2 && block_tables.size(0) == num_seqs &&
+                  cu_seqlens_q.numel() == num_seqs + 1,
+              op, ": need block_tables [S, W], cu_seqlens_q [S+1], "
+              "seq_lens_k [S]");
+  TORCH_CHECK(total_rows <= num_seqs * max_q, op, ": T=", total_rows,
+              " rows exceed S * max_q = ", num_seqs * max_q);
+  TORCH_CHECK(q.stride(2) == 1 && q.stride(1) == head_dim &&
+                  q.stride(0) % 8 == 0 && aligned16(q),
+              op, ": q rows must be dense and 16-byte aligned");
+  TORCH_CHECK(out.is_contiguous() && out.sizes() == q.sizes() &&
+                  reinterpret_cast<uintptr_t>(out.data_ptr()) % 4 == 0,
+              op, ": out must be a contiguous 4-byte aligned [T, Hq, D] tensor");
+  const int64_t width = block_tables.size(1);
+  TORCH_CHECK(num_parts == std::max<int64_t>((width * 16 + 511) / 512, 1) &&
+                  num_parts * ((max_q * g + 15) / 16) <= 65535,
+              op, ": num_parts must be ceil(W * 16 / 512)");
+  float* ml = nullptr;
+  float* acc = nullptr;
+  if (num_parts > 1) {
+    TORCH_CHECK(ml_ws && acc_ws, op, ": workspace required when num_parts > 1");
+    for (const at::Tensor* t : {&*ml_ws, &*acc_ws})
+      TORCH_CHECK(t->scalar_type() == at::kFloat && t->is_contiguous() &&
+                      t->device() == q.device(),
+                  op, ": workspaces must be contiguous fp32 on q's device");
+    TORCH_CHECK(ml_ws->numel() == total_rows * num_heads * num_parts * 2 &&
+                    acc_ws->numel() ==
+                        total_rows * num_heads * num_parts * head_dim,
+                op, ": workspaces must be [T, Hq, P, 2] and [T, Hq, P, D]");
+    ml = ml_ws->data_ptr<float>();
+    acc = acc_ws->data_ptr<float>();
+  }
+  fi::launch_shortq_attn(
+      bf16_ptr(out), ml, acc, bf16_cptr(q), k_cache.data_ptr(),
+      v_cache.data_ptr(), block_tables.data_ptr<int>(),
+      cu_seqlens_q.data_ptr<int>(), seq_lens_k.data_ptr<int>(),
+      static_cast<int>(num_seqs), static_cast<int>(total_rows), q.stride(0),
+      static_cast<int>(width), static_cast<int>(num_kv_heads),
+      static_cast<int>(head_dim), static_cast<int>(g),
+      static_cast<int>(num_parts), static_cast<int>(max_q),
+      static_cast<float>(scale), fp8, current_stream());
 }
 
 // Shape checks shared by the bf16 and fp8 grouped GEMMs (dtype checks
@@ -1369,6 +1453,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("prefill_attention", &prefill_attention, "varlen causal MFMA prefill");
   m.def("prefill_attention_paged", &prefill_attention_paged,
         "varlen causal MFMA prefill over the paged cache (context attention)");
+  m.def("paged_attention_shortq", &paged_attention_shortq,
+        "short-query (<= 32 rows per sequence) paged attention, MFMA QK and PV");
   m.def("moe_gemm", &moe_gemm,
         "grouped MFMA GEMM over block-aligned expert segments "
         "(gate_up=true fuses the SwiGLU epilogue)");

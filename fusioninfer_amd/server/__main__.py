@@ -123,7 +123,10 @@ def parse_args(argv=None):
                    help='JSON: {"method": "ngram", '
                         '"num_speculative_tokens": 4, '
                         '"prompt_lookup_max": 4, "prompt_lookup_min": 2, '
-                        '"sampled_verify": true}')
+                        '"sampled_verify": true, '
+                        '"verify_attention": "prefill"}; '
+                        '"verify_attention": "shortq" runs verify steps on '
+                        'the short-query paged attention kernel')
     p.add_argument("--api-key", default=None,
                    help="bearer token required on every endpoint except "
                         "/health and /metrics (vLLM --api-key)")
@@ -181,6 +184,7 @@ def build_engine_config(args):
             model=raw.get("model"),
             draft_gpu_blocks=raw.get("draft_gpu_blocks"),
             sampled_verify=bool(raw.get("sampled_verify", True)),
+            verify_attention=str(raw.get("verify_attention", "prefill")),
         )
     return EngineConfig(
         model=mc,

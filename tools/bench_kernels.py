@@ -3,7 +3,8 @@
 Usage: python tools/bench_kernels.py
            [prefill|decode|elementwise|lora|sampling|sampling_e2e|penalties|
             penalties_e2e|logprobs|logprobs_e2e|spec_verify|
-            spec_sampled_e2e|logit_mods|guided_spec_e2e|bias_pipelining|all]
+            spec_sampled_e2e|logit_mods|guided_spec_e2e|bias_pipelining|
+            shortq|all]
 Prints per-shape timing + achieved TFLOP/s (attention) or GB/s (memory ops).
 """
 
@@ -1386,6 +1387,121 @@ def bench_mxfp4_moe_a8_wide(rounds=3):
               + f" | {err.item():.3e} | {same} |", flush=True)
 
 
+def bench_shortq(rounds=5, iters=40):
+    """paged_attention_shortq against prefill_attention_paged on the same
+    inputs (5-row verify spans, bf16 cache, D=128), alternating in one
+    process: median device-event us per call over rounds x iters calls.
+    paged_attention_decode on the same cache (one row per sequence) is the
+    bandwidth yardstick. KV bytes = S * Hk * ctx * D * 2 (K and V) * 2 B,
+    read once: the GB/s column is those bytes over the shortq time."""
+    import fusioninfer_amd.ops as ops
+
+    D, n, dev = 128, 5, "cuda"
+    print("== short-query paged attention, 5-row spans, bf16, D=128 ==")
+    print("| Hq/Hk | S | ctx | prefill us | shortq us | prefill/shortq | "
+          "decode(n=1) us | shortq KV GB/s | max abs diff |")
+    print("|---|---|---|---|---|---|---|---|---|")
+    shapes = [(32, 8, S, ctx) for ctx in (1024, 8192) for S in (1, 8, 32)]
+    shapes.append((32, 4, 8, 8192))
+    for hq, hk, S, ctx in shapes:
+        nblk = ctx // 16
+        gen = torch.Generator().manual_seed(0)
+        k = torch.randn(1 + S * nblk, hk, 16, D, generator=gen).to(
+            dev, torch.bfloat16)
+        v = torch.randn(1 + S * nblk, hk, 16, D, generator=gen).to(
+            dev, torch.bfloat16)
+        bt = (1 + torch.randperm(S * nblk, generator=gen)).to(
+            torch.int32).view(S, nblk).to(dev)
+        q = torch.randn(S * n, hq, D, generator=gen).to(dev, torch.bfloat16)
+        cu = torch.arange(0, S * n + 1, n, dtype=torch.int32, device=dev)
+        lens = torch.full((S,), ctx, dtype=torch.int32, device=dev)
+        tiles = ops.build_prefill_tiles([n] * S, device=dev,
+                                        ctx_starts=[ctx - n] * S)
+        q1 = q[::n].contiguous()
+        fns = {
+            "prefill": lambda: ops.prefill_attention_paged(
+                q, k, v, bt, cu, lens, tile_seq=tiles[0], tile_row0=tiles[1]),
+            "shortq": lambda: ops.paged_attention_shortq(
+                q, k, v, bt, cu, lens, max_q=n),
+            "decode": lambda: ops.paged_attention_decode(q1, k, v, bt, lens),
+        }
+        diff = (fns["prefill"]().float() - fns["shortq"]().float()).abs().max()
+        times = {name: [] for name in fns}
+        for fn in fns.values():
+            for _ in range(5):
+                fn()
+        for _ in range(rounds):
+            for name, fn in fns.items():
+                times[name] += _event_times_us(fn, iters)
+        med = {name: _median(t) for name, t in times.items()}
+        gbs = S * hk * ctx * D * 2 * 2 / (med["shortq"] * 1e-6) / 1e9
+        print(f"| {hq}/{hk} | {S} | {ctx} | {med['prefill']:.1f} | "
+              f"{med['shortq']:.1f} | {med['prefill'] / med['shortq']:.2f}x | "
+              f"{med['decode']:.1f} | {gbs:.0f} | {diff.item():.4f} |",
+              flush=True)
+
+
+def bench_shortq_e2e(runs=3):
+    """Per-step wall time of the 4-layer Qwen3-0.6B test engine with 1 and 8
+    greedy n-gram drafting requests (4 draft tokens, 64 tokens each),
+    verify_attention "prefill" against "shortq" from one build, runs
+    alternating. Random weights: the acceptance rate says nothing about
+    real checkpoints."""
+    from fusioninfer_amd.config import (CacheConfig, EngineConfig,
+                                        SchedulerConfig)
+    from fusioninfer_amd.engine.llm_engine import LLMEngine
+    from fusioninfer_amd.engine.sequence import SamplingParams
+    from fusioninfer_amd.engine.spec_decode import SpeculativeConfig
+    from fusioninfer_amd.models.registry import get_model_config
+
+    def engine(mode):
+        mc = get_model_config("Qwen3-0.6B")
+        mc.num_layers = 4
+        cfg = EngineConfig(
+            model=mc,
+            cache=CacheConfig(num_gpu_blocks=2048),
+            scheduler=SchedulerConfig(
+                max_num_seqs=16, max_num_batched_tokens=4096,
+                max_model_len=512,
+            ),
+            seed=7,
+            speculative=SpeculativeConfig(
+                num_speculative_tokens=4, prompt_lookup_min=1,
+                verify_attention=mode),
+        )
+        torch.manual_seed(0)
+        return LLMEngine(cfg, device="cuda:0")
+
+    engines = {m: engine(m) for m in ("prefill", "shortq")}
+
+    def run(eng, n):
+        for i in range(n):
+            eng.add_request([11 + i, 13 + i, 17 + i] * 20,
+                            SamplingParams(max_tokens=64))
+        t0g, steps = eng.num_generated_tokens, 0
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        while eng.has_unfinished():
+            eng.step()
+            steps += 1
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0, steps,
+                eng.num_generated_tokens - t0g)
+
+    print("== engine steps under greedy n-gram speculation (4-layer "
+          "Qwen3-0.6B) ==")
+    print("| requests | verify_attention | run | steps | tokens | ms/step |")
+    print("|---|---|---|---|---|---|")
+    for n in (1, 8):
+        for eng in engines.values():
+            run(eng, n)  # untimed
+        for i in range(runs):
+            for mode, eng in engines.items():
+                dt, steps, toks = run(eng, n)
+                print(f"| {n} | {mode} | {i} | {steps} | {toks} | "
+                      f"{dt / steps * 1e3:.3f} |", flush=True)
+
+
 if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "all"
     torch.manual_seed(0)
@@ -1428,3 +1544,6 @@ if __name__ == "__main__":
         bench_mxfp4_moe_a8()
     if which in ("mxfp4_moe_a8_wide", "all"):
         bench_mxfp4_moe_a8_wide()
+    if which in ("shortq", "all"):
+        bench_shortq()
+        bench_shortq_e2e()

@@ -45,7 +45,8 @@ def build(verbose: bool = True, force: bool = False) -> str:
     from torch.utils import cpp_extension as ce
 
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
-    hdrs = [os.path.join(CSRC, "common.h")]
+    hdrs = [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC))
+            if h.endswith(".h")]
     if not force and os.path.exists(SO_PATH):
         so_mtime = os.path.getmtime(SO_PATH)
         if all(os.path.getmtime(f) < so_mtime for f in srcs + hdrs):

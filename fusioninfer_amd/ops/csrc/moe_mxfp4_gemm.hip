@@ -4,8 +4,8 @@
 //
 // joins the two existing halves: the block-aligned grouped-GEMM contract of
 // moe_gemm.hip (sorted_ids / expert_ids / the n_valid device scalar, static
-// grid, fused SwiGLU epilogue) and the exact e2m1/e8m0 expansion and lane
-// mapping of mxfp4_gemm.hip. Expert weights use the row format mxfp4_linear
+// grid, fused SwiGLU epilogue) and the exact e2m1/e8m0 expansion and W4A16
+// lane mapping of mx_common.h. Expert weights use the row format mxfp4_linear
 // reads, per expert: w_packed [E, NB, K/2] (k even in the low nibble) and
 // w_scale [E, NB, K/32] e8m0 bytes in [8, 247]; NB = 2N for gate_up (gate
 // rows first, then up rows), NB = N for down. Dequantisation is exact, so
@@ -16,7 +16,7 @@
 // the 16 B that hold k = 128 s + 32 g ... + 31 of W row n0 + c: one MX
 // block, one scale byte. Fragment t of it is k = 128 s + 32 g + 8 t + j, and
 // the A operand uses the same permuted k (a contiguous 16 B of the row), as
-// documented at the top of mxfp4_gemm.hip. No bf16 copy of W exists
+// documented in mx_common.h. No bf16 copy of W exists
 // anywhere: packed bytes go from HBM to VGPRs and are expanded there.
 //
 // One template, two instances per epilogue, chosen by block_m:
@@ -42,39 +42,11 @@
 
 #include <hip/hip_runtime.h>
 
-#include "common.h"
+#include "mx_common.h"
 
 namespace fi {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) short short8;
-typedef __attribute__((ext_vector_type(4))) float floatx4;
-typedef __attribute__((ext_vector_type(4))) u32 u32x4;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-
-// 2^(s - 127) for an e8m0 byte s in [1, 254]
-FI_DEV float e8m0_to_f32(u32 s) { return __uint_as_float(s << 23); }
-
-// Eight e2m1 codes of one u32 (k ascending) times `scale` -> 8 bf16
-FI_DEV short8 dequant_fp4x8(u32 w, float scale) {
-  union {
-    bf16x2_t p[4];
-    short8 v;
-  } u;
-#if defined(__HIP_DEVICE_COMPILE__)
-  u.p[0] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 0);
-  u.p[1] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 1);
-  u.p[2] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 2);
-  u.p[3] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 3);
-#else
-  u.v = short8{0, 0, 0, 0, 0, 0, 0, 0};
-#endif
-  return u.v;
-}
-
-// same expression as moe_gemm_kernel's epilogue
-FI_DEV float swiglu(float g, float u) { return (g / (1.f + __expf(-g))) * u; }
 
 // NF W rows per lane (gate, up) of one k-chunk: packed block + scale byte
 template <int NF>

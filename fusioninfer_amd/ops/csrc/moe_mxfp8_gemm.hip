@@ -7,11 +7,12 @@
 //                sum_k dq(a)[row(slot), k] * dq(W[e])[n, k],
 //                sum_k dq(a)[row(slot), k] * dq(W[e])[N + n, k] ) ) )
 //
-// joins the block-aligned grouped-GEMM contract of moe_mxfp4_gemm.hip
+// joins the block-aligned grouped-GEMM contract of moe_gemm_mxfp4
 // (sorted_ids / expert_ids / the n_valid device scalar, static grid; an
 // m-tile is 128 padded slots of one expert) and the operand movement of
-// mxfp4_mxfp8_gemm_kernel (mxfp8_gemm.hip, whose header documents the lane
-// layout of v_mfma_scale_f32_16x16x128_f8f6f4). Expert weights are the
+// mxfp4_mxfp8_gemm_kernel, in the lane layout of
+// v_mfma_scale_f32_16x16x128_f8f6f4 documented in mx_common.h, which also
+// holds the operand helpers and both epilogues. Expert weights are the
 // tensors moe_gemm_mxfp4 reads, unchanged: w_packed [E, NB, K/2] and w_scale
 // [E, NB, K/32], NB = 2N (gate rows, then up rows) for gate_up. Neither
 // operand is expanded, nothing is repacked, and nothing is indexed from
@@ -42,12 +43,10 @@
 // lane holds m = l & 15 and n = 4 (l >> 4) ... + 3 of every fragment, so the
 // gate and the up value of one act element sit in the same lane and element,
 // and a wave owns whole 32-column MX blocks of an act row: the epilogue
-// needs no LDS. Per m-fragment: v = bf16(swiglu(g, u)); block amax over the
-// lane's 2 x 4 values and across the four lane groups (shfl_xor 16, 32); the
-// scale byte, scaling, clamp, convert and -0 rule of quant_mxfp8_rows; one
-// 4 B store per lane per n-fragment, and lane group 0 stores the scale byte.
-// The output equals reference.mxfp8_quant_rows on the bf16 act row, bit for
-// bit; the bf16 act tensor never exists.
+// (store_swiglu_mxfp8_tile, mx_common.h) needs no LDS and applies the scale
+// byte, scaling, clamp, convert and -0 rule of quant_mxfp8_rows. The output
+// equals reference.mxfp8_quant_rows on the bf16 act row, bit for bit; the
+// bf16 act tensor never exists.
 //
 // Determinism: every accumulator sums the K steps in ascending order and
 // nothing is split or combined across waves, so a (token, expert) row's bits
@@ -60,68 +59,13 @@
 
 #include <type_traits>
 
-#include "common.h"
+#include "mx_common.h"
 
 namespace fi {
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) float floatx4;
-typedef __attribute__((ext_vector_type(4))) u32 u32x4;
-typedef __attribute__((ext_vector_type(8))) int intx8;
-typedef __attribute__((ext_vector_type(2))) short short2_t;
-
 constexpr int kBlockM = 128;     // slots of an m-tile
-constexpr int kRowBytes = 144;   // LDS row: 128 B of e4m3 + 16 B pad
-constexpr int kFmtFp8 = 0;       // e4m3
-constexpr int kFmtFp4 = 4;       // e2m1
-
-// nothing is scheduled across this point
-#if defined(__HIP_DEVICE_COMPILE__)
-#define FI_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
-#else
-#define FI_SCHED_FENCE()
-#endif
-
-// D = A(fp4, 16 x 128) * B(fp8, 128 x 16) + C with per-lane block scales
-FI_DEV floatx4 mfma_w4a8(u32x4 w, u32 wscale, intx8 x, u32 xscale,
-                         floatx4 acc) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  const intx8 a = {static_cast<int>(w[0]), static_cast<int>(w[1]),
-                   static_cast<int>(w[2]), static_cast<int>(w[3]), 0, 0, 0, 0};
-  return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
-      a, x, acc, kFmtFp4, kFmtFp8, 0, static_cast<int>(wscale), 0,
-      static_cast<int>(xscale));
-#else
-  return acc;
-#endif
-}
-
-// same expression as moe_mxfp4_gemm_kernel's epilogue
-FI_DEV float swiglu(float g, float u) { return (g / (1.f + __expf(-g))) * u; }
-
-// four scaled, clamped values -> four e4m3 bytes (v[0] lowest), -0 as +0
-FI_DEV u32 pack_fp8x4(const float* v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  union {
-    u32 u;
-    short2_t s;
-  } c;
-  c.u = 0;
-  // the block scale is already applied (exactly) because the clamp needs
-  // the scaled value; the convert itself runs at scale 1
-  c.s = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(c.s, v[0], v[1], 1.0f, false);
-  c.s = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(c.s, v[2], v[3], 1.0f, true);
-  u32 w = c.u;
-  if ((w & 0x0000007fu) == 0) w &= 0xffffff00u;
-  if ((w & 0x00007f00u) == 0) w &= 0xffff00ffu;
-  if ((w & 0x007f0000u) == 0) w &= 0xff00ffffu;
-  if ((w & 0x7f000000u) == 0) w &= 0x00ffffffu;
-  return w;
-#else
-  return 0;
-#endif
-}
 
 template <bool GATE_UP>
 __global__ __launch_bounds__(256, 2) void moe_mxfp4_mxfp8_gemm_kernel(
@@ -179,15 +123,7 @@ __global__ __launch_bounds__(256, 2) void moe_mxfp4_mxfp8_gemm_kernel(
   // W fragments and their scale bytes: lane -> row r, MX block g of the step
   const unsigned char* wp[4];
   const unsigned char* wsp[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    // gate_up: fragments 0, 1 are gate rows, 2, 3 the matching up rows
-    const int col = GATE_UP ? wn + 16 * (j & 1) + r : wn + 16 * j + r;
-    const int64_t n =
-        wrow0 + (GATE_UP && j >= 2 ? N : 0) + min(col, N - 1);
-    wp[j] = wq + n * (K / 2) + 16 * g;
-    wsp[j] = ws + n * (K / 32) + g;
-  }
+  w_frag_ptrs<GATE_UP>(wp, wsp, wq, ws, wrow0, wn, r, g, N, K);
   // x fragment: bytes 16 g ... + 15 and 64 + 16 g ... + 15 of the row's step
   const int xfrag = (wm + r) * kRowBytes + 16 * g;
 
@@ -227,14 +163,7 @@ __global__ __launch_bounds__(256, 2) void moe_mxfp4_mxfp8_gemm_kernel(
     const unsigned char* buf = xl[p];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const u32x4 lo =
-          *reinterpret_cast<const u32x4*>(buf + xfrag + 16 * i * kRowBytes);
-      const u32x4 hi = *reinterpret_cast<const u32x4*>(
-          buf + xfrag + 16 * i * kRowBytes + 64);
-      const intx8 xv = {static_cast<int>(lo[0]), static_cast<int>(lo[1]),
-                        static_cast<int>(lo[2]), static_cast<int>(lo[3]),
-                        static_cast<int>(hi[0]), static_cast<int>(hi[1]),
-                        static_cast<int>(hi[2]), static_cast<int>(hi[3])};
+      const intx8 xv = lds_read_a8_frag(buf + xfrag + 16 * i * kRowBytes);
       // byte g of the row's dword (one v_bfe_u32)
       const u32 xsc = (sl[p][wm + 16 * i + r] >> (8 * g)) & 0xffu;
 #pragma unroll
@@ -278,65 +207,11 @@ __global__ __launch_bounds__(256, 2) void moe_mxfp4_mxfp8_gemm_kernel(
   }
   if (nsteps & 1) mfmas(P0{});
 
-  // lane -> slot r of each m fragment, columns 4 g ... + 3 of each n
-  // fragment
-  if constexpr (!GATE_UP) {
-    u16* out = static_cast<u16*>(out_v);
-    // N % 16 == 0, so a fragment is stored whole or not at all
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int n = wn + 16 * j + 4 * g;
-      if (n < N) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int64_t slot = slot0 + wm + 16 * i + r;
-          bf16x4 o;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) o.h[e] = f32_to_bf16(acc[j][i][e]);
-          *reinterpret_cast<bf16x4*>(out + slot * N + n) = o;
-        }
-      }
-    }
-  } else {
-    unsigned char* out = static_cast<unsigned char*>(out_v);
-    // N % 32 == 0, so a wave's MX block of act columns is whole or absent
-    // (wave-uniform; every barrier is behind us)
-    if (wn < N) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int64_t slot = slot0 + wm + 16 * i + r;
-        float v[2][4];
-        float amax = 0.f;
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            v[j][e] = bf16_to_f32(
-                f32_to_bf16(swiglu(acc[j][i][e], acc[j + 2][i][e])));
-            amax = fmaxf(amax, fabsf(v[j][e]));
-          }
-        amax = fmaxf(amax, __shfl_xor(amax, 16, 64));
-        amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
-        // quant_mxfp8_rows' rule: floor(log2(amax)) is the exponent field;
-        // a subnormal amax reads 0 and clamps to 8 as its true exponent would
-        int s = static_cast<int>((__float_as_uint(amax) >> 23) & 0xff) - 8;
-        s = min(max(s, 8), 247);
-        if (amax == 0.f) s = 127;
-        const float inv = __uint_as_float(static_cast<u32>(254 - s) << 23);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          // the convert gives NaN past 448 instead of saturating: clamp first
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            v[j][e] = fminf(fmaxf(v[j][e] * inv, -448.f), 448.f);
-          *reinterpret_cast<u32*>(out + slot * N + wn + 16 * j + 4 * g) =
-              pack_fp8x4(v[j]);
-        }
-        if (g == 0)
-          out_scale[slot * (N / 32) + wn / 32] = static_cast<unsigned char>(s);
-      }
-    }
-  }
+  if constexpr (!GATE_UP)
+    store_bf16_tile(static_cast<u16*>(out_v), acc, slot0 + wm, wn, r, g, N);
+  else
+    store_swiglu_mxfp8_tile(static_cast<unsigned char*>(out_v), out_scale, acc,
+                            slot0 + wm, wn, r, g, N);
 }
 
 // ---------------------------------------------------------------------------
@@ -425,15 +300,7 @@ __global__ __launch_bounds__(256, 2) void moe_mxfp4_mxfp8_gemm32_kernel(
   // W fragments and their scale bytes: lane -> row r, MX block g of the step
   const unsigned char* wp[4];
   const unsigned char* wsp[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    // gate_up: fragments 0, 1 are gate rows, 2, 3 the matching up rows
-    const int col = GATE_UP ? wn + 16 * (j & 1) + r : wn + 16 * j + r;
-    const int64_t n =
-        wrow0 + (GATE_UP && j >= 2 ? N : 0) + min(col, N - 1);
-    wp[j] = wq + n * (K / 2) + 16 * g;
-    wsp[j] = ws + n * (K / 32) + g;
-  }
+  w_frag_ptrs<GATE_UP>(wp, wsp, wq, ws, wrow0, wn, r, g, N, K);
   // x fragment: bytes 16 g ... + 15 and 64 + 16 g ... + 15 of the row's step
   const int xfrag = r * kRowBytes + 16 * g;
 
@@ -494,14 +361,7 @@ __global__ __launch_bounds__(256, 2) void moe_mxfp4_mxfp8_gemm32_kernel(
     const unsigned char* buf = xl[cur] + q * kPanelBytes + xfrag;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-      const u32x4 lo =
-          *reinterpret_cast<const u32x4*>(buf + 16 * i * kRowBytes);
-      const u32x4 hi =
-          *reinterpret_cast<const u32x4*>(buf + 16 * i * kRowBytes + 64);
-      const intx8 xv = {static_cast<int>(lo[0]), static_cast<int>(lo[1]),
-                        static_cast<int>(lo[2]), static_cast<int>(lo[3]),
-                        static_cast<int>(hi[0]), static_cast<int>(hi[1]),
-                        static_cast<int>(hi[2]), static_cast<int>(hi[3])};
+      const intx8 xv = lds_read_a8_frag(buf + 16 * i * kRowBytes);
       // byte g of the row's dword (one v_bfe_u32)
       const u32 xsc = (sl[cur][32 * q + 16 * i + r] >> (8 * g)) & 0xffu;
 #pragma unroll
@@ -538,65 +398,11 @@ __global__ __launch_bounds__(256, 2) void moe_mxfp4_mxfp8_gemm32_kernel(
   if (rem >= 2) step(P1{}, s + 1);
   if (rem == 3) step(P2{}, s + 2);
 
-  // lane -> slot r of each m fragment, columns 4 g ... + 3 of each n
-  // fragment
-  if constexpr (!GATE_UP) {
-    u16* out = static_cast<u16*>(out_v);
-    // N % 16 == 0, so a fragment is stored whole or not at all
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int n = wn + 16 * j + 4 * g;
-      if (n < N) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          const int64_t slot = slot0 + 16 * i + r;
-          bf16x4 o;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) o.h[e] = f32_to_bf16(acc[j][i][e]);
-          *reinterpret_cast<bf16x4*>(out + slot * N + n) = o;
-        }
-      }
-    }
-  } else {
-    unsigned char* out = static_cast<unsigned char*>(out_v);
-    // N % 32 == 0, so a wave's MX block of act columns is whole or absent
-    // (wave-uniform; every barrier is behind us)
-    if (wn < N) {
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int64_t slot = slot0 + 16 * i + r;
-        float v[2][4];
-        float amax = 0.f;
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            v[j][e] = bf16_to_f32(
-                f32_to_bf16(swiglu(acc[j][i][e], acc[j + 2][i][e])));
-            amax = fmaxf(amax, fabsf(v[j][e]));
-          }
-        amax = fmaxf(amax, __shfl_xor(amax, 16, 64));
-        amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
-        // quant_mxfp8_rows' rule, as in the 128-slot kernel
-        int sb = static_cast<int>((__float_as_uint(amax) >> 23) & 0xff) - 8;
-        sb = min(max(sb, 8), 247);
-        if (amax == 0.f) sb = 127;
-        const float inv = __uint_as_float(static_cast<u32>(254 - sb) << 23);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          // the convert gives NaN past 448 instead of saturating: clamp first
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            v[j][e] = fminf(fmaxf(v[j][e] * inv, -448.f), 448.f);
-          *reinterpret_cast<u32*>(out + slot * N + wn + 16 * j + 4 * g) =
-              pack_fp8x4(v[j]);
-        }
-        if (g == 0)
-          out_scale[slot * (N / 32) + wn / 32] =
-              static_cast<unsigned char>(sb);
-      }
-    }
-  }
+  if constexpr (!GATE_UP)
+    store_bf16_tile(static_cast<u16*>(out_v), acc, slot0, wn, r, g, N);
+  else
+    store_swiglu_mxfp8_tile(static_cast<unsigned char*>(out_v), out_scale, acc,
+                            slot0, wn, r, g, N);
 }
 
 }  // namespace

@@ -12,11 +12,8 @@
 // mxfp4_linear_kernel<MT, NT> is the small-M, weight-streaming case: one
 // workgroup owns NT 16-column tiles and MT 16-row tiles; W goes straight
 // from HBM to VGPRs (16 B per lane = one MX block = one scale byte), is
-// expanded to four bf16 B fragments and fed to mfma_f32_16x16x32_bf16.
-// Lane l (column c = l & 15, group g = l >> 4) of k-chunk s (128 k) holds
-// k = 128 s + 32 g ... + 31; fragment t of it is k = 128 s + 32 g + 8 t + j.
-// The A operand uses the same permuted k: lane (row r, group g) element j of
-// step t is x[r][128 s + 32 g + 8 t + j], a contiguous 16 B.
+// expanded to four bf16 B fragments and fed to mfma_f32_16x16x32_bf16, in the
+// W4A16 lane mapping documented in mx_common.h.
 //
 // The four waves split K in interleaved pairs of chunks (a pair is one
 // 128 B line of every W row) and combine through LDS in fixed wave order
@@ -29,37 +26,11 @@
 
 #include <hip/hip_runtime.h>
 
-#include "common.h"
+#include "mx_common.h"
 
 namespace fi {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) short short8;
-typedef __attribute__((ext_vector_type(4))) float floatx4;
-typedef __attribute__((ext_vector_type(4))) u32 u32x4;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-
-// 2^(s - 127) for an e8m0 byte s in [1, 254]
-FI_DEV float e8m0_to_f32(u32 s) { return __uint_as_float(s << 23); }
-
-// Eight e2m1 codes of one u32 (k ascending: byte b holds k = 2b in its low
-// nibble, k = 2b + 1 in its high nibble) times `scale` -> 8 bf16.
-FI_DEV short8 dequant_fp4x8(u32 w, float scale) {
-  union {
-    bf16x2_t p[4];
-    short8 v;
-  } u;
-#if defined(__HIP_DEVICE_COMPILE__)
-  u.p[0] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 0);
-  u.p[1] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 1);
-  u.p[2] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 2);
-  u.p[3] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 3);
-#else
-  u.v = short8{0, 0, 0, 0, 0, 0, 0, 0};
-#endif
-  return u.v;
-}
 
 // U = chunk pairs a wave keeps in flight per loop trip
 template <int MT, int NT, int U>

@@ -6,23 +6,8 @@
 // with fp32 sums. W is the tensor pair mxfp4_linear reads (e2m1 nibbles, k
 // even in the low nibble, one e8m0 byte per 32 k); x_q is e4m3 with one e8m0
 // byte per 32 k of a row. Neither operand is ever expanded: both block
-// scales are applied by v_mfma_scale_f32_16x16x128_f8f6f4.
-//
-// Fragment layout of one 16x16x128 step, as established by the one-hot tests
-// (tests/test_mxfp4_a8_gpu.py). Lane l = 16 g + r holds row r of its 16-row
-// tile, for both operands; k below is relative to the step's first k, 128 s:
-//   * fp4 (W, srcA), 4 operand VGPRs: VGPR v, nibble q is k = 32 g + 8 v + q.
-//     A lane holds one whole MX block, ascending: exactly the 16 B per lane
-//     mxfp4_linear loads, no unpacking;
-//   * fp8 (x, srcB), 8 operand VGPRs: VGPR v, byte b is
-//     k = 64 (v / 4) + 16 g + 4 (v % 4) + b. A lane holds two 16 B runs, 64 k
-//     apart, i.e. halves of the MX blocks g / 2 and 2 + g / 2: the fp8
-//     operand is not laid out like the fp4 one;
-//   * scales follow k, not the data lanes: the e8m0 byte of MX block g
-//     (k = 32 g ... + 31) of row r is taken from byte 0 (opsel 0) of the
-//     scale VGPR of lane 16 g + r, for srcA and srcB alike.
-// W is srcA, so D row = n and D column = m: lane l holds m = l & 15 and the
-// four consecutive columns n = 4 (l >> 4) ... + 3, one 8 B store.
+// scales are applied by v_mfma_scale_f32_16x16x128_f8f6f4, whose lane layout
+// is documented in mx_common.h.
 //
 // mxfp4_mxfp8_gemm_kernel: 256 threads own a 128 x 128 macro-tile, the four
 // waves 2 x 2, each with a 4 x 4 register block of 16x16 accumulators (64
@@ -49,48 +34,22 @@
 //
 // quant_mxfp8_rows_kernel: two lanes own one MX block (16 elements each, two
 // 16 B loads, one 16 B store), the block amax takes one cross-lane step, and
-// the scale is read off the amax exponent. No LDS.
+// the scale is read off the amax exponent (mxfp8_block_scale of mx_common.h,
+// the rule the fused MoE epilogue shares). No LDS. Its clamp, convert and -0
+// steps must equal pack_fp8x4 of mx_common.h; they stay written out here
+// because going through pack_fp8x4 costs this kernel a VGPR (27 against 26).
 
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
 
-#include "common.h"
+#include "mx_common.h"
 
 namespace fi {
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) float floatx4;
-typedef __attribute__((ext_vector_type(4))) u32 u32x4;
-typedef __attribute__((ext_vector_type(8))) int intx8;
-typedef __attribute__((ext_vector_type(2))) short short2_t;
-
 constexpr int kTile = 128;       // macro-tile rows and columns
-constexpr int kRowBytes = 144;   // LDS row: 128 B of e4m3 + 16 B pad
-constexpr int kFmtFp8 = 0;       // e4m3
-constexpr int kFmtFp4 = 4;       // e2m1
-
-// nothing is scheduled across this point
-#if defined(__HIP_DEVICE_COMPILE__)
-#define FI_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
-#else
-#define FI_SCHED_FENCE()
-#endif
-
-// D = A(fp4, 16 x 128) * B(fp8, 128 x 16) + C with per-lane block scales
-FI_DEV floatx4 mfma_w4a8(u32x4 w, u32 wscale, intx8 x, u32 xscale,
-                         floatx4 acc) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  const intx8 a = {static_cast<int>(w[0]), static_cast<int>(w[1]),
-                   static_cast<int>(w[2]), static_cast<int>(w[3]), 0, 0, 0, 0};
-  return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
-      a, x, acc, kFmtFp4, kFmtFp8, 0, static_cast<int>(wscale), 0,
-      static_cast<int>(xscale));
-#else
-  return acc;
-#endif
-}
 
 __global__ __launch_bounds__(256, 2) void mxfp4_mxfp8_gemm_kernel(
     u16* __restrict__ out,                  // [M, N] bf16
@@ -172,14 +131,7 @@ __global__ __launch_bounds__(256, 2) void mxfp4_mxfp8_gemm_kernel(
     const unsigned char* buf = xl[p];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const u32x4 lo =
-          *reinterpret_cast<const u32x4*>(buf + xfrag + 16 * i * kRowBytes);
-      const u32x4 hi = *reinterpret_cast<const u32x4*>(
-          buf + xfrag + 16 * i * kRowBytes + 64);
-      const intx8 xv = {static_cast<int>(lo[0]), static_cast<int>(lo[1]),
-                        static_cast<int>(lo[2]), static_cast<int>(lo[3]),
-                        static_cast<int>(hi[0]), static_cast<int>(hi[1]),
-                        static_cast<int>(hi[2]), static_cast<int>(hi[3])};
+      const intx8 xv = lds_read_a8_frag(buf + xfrag + 16 * i * kRowBytes);
 #pragma unroll
       for (int j = 0; j < 4; ++j)
         acc[j][i] = mfma_w4a8(wv[p][j], wsc[p][j], xv, xsc[p][i], acc[j][i]);
@@ -286,12 +238,8 @@ __global__ __launch_bounds__(256) void quant_mxfp8_rows_kernel(
     amax = fmaxf(amax, fabsf(f[e]));
   }
   amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
-  // floor(log2(amax)) is the exponent field; a subnormal amax reads 0 and
-  // clamps to 8 as its true exponent would
-  int s = static_cast<int>((__float_as_uint(amax) >> 23) & 0xff) - 8;
-  s = min(max(s, 8), 247);
-  if (amax == 0.f) s = 127;
-  const float inv = __uint_as_float(static_cast<u32>(254 - s) << 23);
+  float inv;
+  const int s = mxfp8_block_scale(amax, &inv);
   u32x4 q = {0, 0, 0, 0};
 #pragma unroll
   for (int e = 0; e < 16; e += 2) {

@@ -908,28 +908,81 @@ void mxfp4_dequant(at::Tensor out, at::Tensor w_packed, at::Tensor w_scale) {
       current_stream());
 }
 
+// shared checks of the ops on MXFP8 rows: q [rows, K] e4m3 and scale
+// [rows, K/32] uint8, both contiguous on one GPU
+void check_mxfp8_rows(const char* op, const at::Tensor& q,
+                      const at::Tensor& scale) {
+  TORCH_CHECK(q.is_cuda() && scale.is_cuda() &&
+                  q.scalar_type() == at::kFloat8_e4m3fn &&
+                  scale.scalar_type() == at::kByte,
+              op, ": MXFP8 rows must be e4m3 and their scale uint8, on GPU");
+  TORCH_CHECK(q.dim() == 2 && scale.dim() == 2 && q.is_contiguous() &&
+                  scale.is_contiguous(),
+              op, ": MXFP8 rows and their scale must be 2-D and contiguous");
+  TORCH_CHECK(q.size(1) % 32 == 0 && scale.size(0) == q.size(0) &&
+                  scale.size(1) == q.size(1) / 32,
+              op, ": the scale of MXFP8 rows [rows, K] must be [rows, K/32]");
+  TORCH_CHECK(q.get_device() == scale.get_device(),
+              op, ": tensors must share one device");
+}
+
+// shared checks of the grouped MXFP4 ops, once K and NB are known to be
+// valid: the weight pair w_packed [E, NB, K/2] / w_scale [E, NB, K/32] uint8,
+// the routing triple, out's padded rows in whole m-tiles, all on out's device
+void check_moe_mxfp4(const char* op, const at::Tensor& out,
+                     const at::Tensor& w_packed, const at::Tensor& w_scale,
+                     const at::Tensor& sorted_ids,
+                     const at::Tensor& expert_ids, const at::Tensor& n_valid,
+                     int64_t K, int64_t NB, int64_t block_m) {
+  TORCH_CHECK(w_packed.is_cuda() && w_scale.is_cuda() &&
+                  w_packed.scalar_type() == at::kByte &&
+                  w_scale.scalar_type() == at::kByte &&
+                  w_packed.dim() == 3 && w_scale.dim() == 3 &&
+                  w_packed.is_contiguous() && w_scale.is_contiguous(),
+              op, ": weights must be contiguous 3-D uint8 on GPU");
+  TORCH_CHECK(sorted_ids.is_cuda() && expert_ids.is_cuda() &&
+                  n_valid.is_cuda() && sorted_ids.scalar_type() == at::kInt &&
+                  expert_ids.scalar_type() == at::kInt &&
+                  n_valid.scalar_type() == at::kInt &&
+                  sorted_ids.is_contiguous() && expert_ids.is_contiguous() &&
+                  n_valid.numel() == 1,
+              op, ": sorted_ids, expert_ids, n_valid must be contiguous int32 "
+              "on GPU");
+  const int64_t PM = out.size(0);
+  TORCH_CHECK(PM >= block_m && PM % block_m == 0 && PM < (1LL << 31),
+              op, ": padded rows must be a positive multiple of block_m");
+  TORCH_CHECK(w_packed.size(0) >= 1 && w_packed.size(1) == NB &&
+                  w_packed.size(2) == K / 2 &&
+                  w_scale.size(0) == w_packed.size(0) &&
+                  w_scale.size(1) == NB && w_scale.size(2) == K / 32,
+              op, ": need w_packed [E, NB, K/2] and w_scale [E, NB, K/32]");
+  TORCH_CHECK(expert_ids.numel() >= PM / block_m && sorted_ids.numel() >= PM,
+              op, ": sorted_ids / expert_ids too short");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(w_packed.data_ptr()) % 16 == 0,
+              op, ": w_packed must be 16-byte aligned");
+  const auto dev = out.get_device();
+  TORCH_CHECK(w_packed.get_device() == dev && w_scale.get_device() == dev &&
+                  sorted_ids.get_device() == dev &&
+                  expert_ids.get_device() == dev &&
+                  n_valid.get_device() == dev,
+              op, ": tensors must share one device");
+}
+
 // x [M, K] bf16 -> x_q [M, K] e4m3 and x_scale [M, K/32] e8m0 (MXFP8 rows)
 void quant_mxfp8_rows(at::Tensor x_q, at::Tensor x_scale, at::Tensor x) {
   CHECK_BF16_CUDA(x);
-  TORCH_CHECK(x_q.is_cuda() && x_scale.is_cuda() &&
-                  x_q.scalar_type() == at::kFloat8_e4m3fn &&
-                  x_scale.scalar_type() == at::kByte,
-              "quant_mxfp8_rows: x_q must be e4m3 and x_scale uint8, on GPU");
-  TORCH_CHECK(x.dim() == 2 && x_q.dim() == 2 && x_scale.dim() == 2 &&
-                  x.is_contiguous() && x_q.is_contiguous() &&
-                  x_scale.is_contiguous(),
-              "quant_mxfp8_rows: tensors must be 2-D and contiguous");
+  check_mxfp8_rows("quant_mxfp8_rows", x_q, x_scale);
+  TORCH_CHECK(x.dim() == 2 && x.is_contiguous(),
+              "quant_mxfp8_rows: x must be 2-D and contiguous");
   const int64_t M = x.size(0), K = x.size(1);
   TORCH_CHECK(M >= 1 && K >= 128 && K % 128 == 0 && x_q.size(0) == M &&
-                  x_q.size(1) == K && x_scale.size(0) == M &&
-                  x_scale.size(1) == K / 32,
+                  x_q.size(1) == K,
               "quant_mxfp8_rows: need x [M, K], x_q [M, K], x_scale "
               "[M, K/32], K % 128 == 0");
   TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0 &&
                   reinterpret_cast<uintptr_t>(x_q.data_ptr()) % 16 == 0,
               "quant_mxfp8_rows: x and x_q must be 16-byte aligned");
-  TORCH_CHECK(x.get_device() == x_q.get_device() &&
-                  x.get_device() == x_scale.get_device(),
+  TORCH_CHECK(x.get_device() == x_q.get_device(),
               "quant_mxfp8_rows: tensors must share one device");
   const int64_t nhalves = M * (K / 16);
   TORCH_CHECK(nhalves / 256 < (1LL << 31) - 1, "quant_mxfp8_rows: too large");
@@ -944,19 +997,11 @@ void mxfp4_mxfp8_linear(at::Tensor out, at::Tensor x_q, at::Tensor x_scale,
   CHECK_BF16_CUDA(out);
   int64_t N, K;
   check_mxfp4_weight(w_packed, w_scale, &N, &K);
-  TORCH_CHECK(x_q.is_cuda() && x_scale.is_cuda() &&
-                  x_q.scalar_type() == at::kFloat8_e4m3fn &&
-                  x_scale.scalar_type() == at::kByte,
-              "mxfp4_mxfp8_linear: x_q must be e4m3 and x_scale uint8, on "
-              "GPU");
-  TORCH_CHECK(x_q.dim() == 2 && x_scale.dim() == 2 && out.dim() == 2 &&
-                  x_q.is_contiguous() && x_scale.is_contiguous() &&
-                  out.is_contiguous(),
-              "mxfp4_mxfp8_linear: x_q, x_scale and out must be 2-D and "
-              "contiguous");
+  check_mxfp8_rows("mxfp4_mxfp8_linear", x_q, x_scale);
+  TORCH_CHECK(out.dim() == 2 && out.is_contiguous(),
+              "mxfp4_mxfp8_linear: out must be 2-D and contiguous");
   const int64_t M = x_q.size(0);
   TORCH_CHECK(M >= 1 && M <= 65535 * 128 && x_q.size(1) == K &&
-                  x_scale.size(0) == M && x_scale.size(1) == K / 32 &&
                   out.size(0) == M && out.size(1) == N,
               "mxfp4_mxfp8_linear: need x_q [M, K], x_scale [M, K/32], out "
               "[M, N], 1 <= M <= 8388480");
@@ -965,7 +1010,6 @@ void mxfp4_mxfp8_linear(at::Tensor out, at::Tensor x_q, at::Tensor x_scale,
               "mxfp4_mxfp8_linear: x_q must be 16-byte and out 8-byte "
               "aligned");
   TORCH_CHECK(x_q.get_device() == out.get_device() &&
-                  x_q.get_device() == x_scale.get_device() &&
                   x_q.get_device() == w_packed.get_device() &&
                   x_q.get_device() == w_scale.get_device(),
               "mxfp4_mxfp8_linear: tensors must share one device");
@@ -1000,20 +1044,6 @@ void moe_gemm_mxfp4(at::Tensor out, at::Tensor a, at::Tensor w_packed,
   TORCH_CHECK(out.dim() == 2 && a.dim() == 2 && out.is_contiguous() &&
                   a.is_contiguous(),
               "moe_gemm_mxfp4: out and a must be 2-D and contiguous");
-  TORCH_CHECK(w_packed.is_cuda() && w_scale.is_cuda() &&
-                  w_packed.scalar_type() == at::kByte &&
-                  w_scale.scalar_type() == at::kByte &&
-                  w_packed.dim() == 3 && w_scale.dim() == 3 &&
-                  w_packed.is_contiguous() && w_scale.is_contiguous(),
-              "moe_gemm_mxfp4: weights must be contiguous 3-D uint8 on GPU");
-  TORCH_CHECK(sorted_ids.is_cuda() && expert_ids.is_cuda() &&
-                  n_valid.is_cuda() && sorted_ids.scalar_type() == at::kInt &&
-                  expert_ids.scalar_type() == at::kInt &&
-                  n_valid.scalar_type() == at::kInt &&
-                  sorted_ids.is_contiguous() && expert_ids.is_contiguous() &&
-                  n_valid.numel() == 1,
-              "moe_gemm_mxfp4: sorted_ids, expert_ids, n_valid must be "
-              "contiguous int32 on GPU");
   TORCH_CHECK(block_m == 16 || block_m == 128,
               "moe_gemm_mxfp4: block_m must be 16 or 128");
   const int64_t K = a.size(1);
@@ -1023,27 +1053,13 @@ void moe_gemm_mxfp4(at::Tensor out, at::Tensor a, at::Tensor w_packed,
   TORCH_CHECK(K >= 128 && K % 128 == 0 && N >= 16 && N % 16 == 0 &&
                   K < (1LL << 31) && NB < (1LL << 31),
               "moe_gemm_mxfp4: need K % 128 == 0 and N % 16 == 0");
-  TORCH_CHECK(PM >= block_m && PM % block_m == 0 && PM < (1LL << 31),
-              "moe_gemm_mxfp4: padded rows must be block_m-aligned");
-  TORCH_CHECK(w_packed.size(0) >= 1 && w_packed.size(1) == NB &&
-                  w_packed.size(2) == K / 2 &&
-                  w_scale.size(0) == w_packed.size(0) &&
-                  w_scale.size(1) == NB && w_scale.size(2) == K / 32,
-              "moe_gemm_mxfp4: need w_packed [E, NB, K/2] and w_scale "
-              "[E, NB, K/32]");
-  TORCH_CHECK(expert_ids.numel() >= PM / block_m &&
-                  sorted_ids.numel() >= PM && a.size(0) >= 1 &&
-                  (gate_up || a.size(0) >= PM),
-              "moe_gemm_mxfp4: sorted_ids / expert_ids / a too short");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(a.data_ptr()) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(w_packed.data_ptr()) % 16 == 0,
-              "moe_gemm_mxfp4: a and w_packed must be 16-byte aligned");
-  const auto dev = out.get_device();
-  TORCH_CHECK(a.get_device() == dev && w_packed.get_device() == dev &&
-                  w_scale.get_device() == dev &&
-                  sorted_ids.get_device() == dev &&
-                  expert_ids.get_device() == dev &&
-                  n_valid.get_device() == dev,
+  check_moe_mxfp4("moe_gemm_mxfp4", out, w_packed, w_scale, sorted_ids,
+                  expert_ids, n_valid, K, NB, block_m);
+  TORCH_CHECK(a.size(0) >= 1 && (gate_up || a.size(0) >= PM),
+              "moe_gemm_mxfp4: a too short");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(a.data_ptr()) % 16 == 0,
+              "moe_gemm_mxfp4: a must be 16-byte aligned");
+  TORCH_CHECK(a.get_device() == out.get_device(),
               "moe_gemm_mxfp4: tensors must share one device");
   fi::launch_moe_gemm_mxfp4(
       bf16_ptr(out), bf16_cptr(a),
@@ -1074,28 +1090,7 @@ void moe_gemm_mxfp4_mxfp8(at::Tensor out, at::Tensor a_q, at::Tensor a_scale,
                       (gate_up ? at::kFloat8_e4m3fn : at::kBFloat16),
               "moe_gemm_mxfp4_mxfp8: out must be a contiguous 2-D GPU tensor, "
               "e4m3 with gate_up and bf16 without");
-  TORCH_CHECK(a_q.is_cuda() && a_scale.is_cuda() &&
-                  a_q.scalar_type() == at::kFloat8_e4m3fn &&
-                  a_scale.scalar_type() == at::kByte && a_q.dim() == 2 &&
-                  a_scale.dim() == 2 && a_q.is_contiguous() &&
-                  a_scale.is_contiguous(),
-              "moe_gemm_mxfp4_mxfp8: a_q must be e4m3 and a_scale uint8, 2-D "
-              "and contiguous on GPU");
-  TORCH_CHECK(w_packed.is_cuda() && w_scale.is_cuda() &&
-                  w_packed.scalar_type() == at::kByte &&
-                  w_scale.scalar_type() == at::kByte &&
-                  w_packed.dim() == 3 && w_scale.dim() == 3 &&
-                  w_packed.is_contiguous() && w_scale.is_contiguous(),
-              "moe_gemm_mxfp4_mxfp8: weights must be contiguous 3-D uint8 on "
-              "GPU");
-  TORCH_CHECK(sorted_ids.is_cuda() && expert_ids.is_cuda() &&
-                  n_valid.is_cuda() && sorted_ids.scalar_type() == at::kInt &&
-                  expert_ids.scalar_type() == at::kInt &&
-                  n_valid.scalar_type() == at::kInt &&
-                  sorted_ids.is_contiguous() && expert_ids.is_contiguous() &&
-                  n_valid.numel() == 1,
-              "moe_gemm_mxfp4_mxfp8: sorted_ids, expert_ids, n_valid must be "
-              "contiguous int32 on GPU");
+  check_mxfp8_rows("moe_gemm_mxfp4_mxfp8", a_q, a_scale);
   const int64_t K = a_q.size(1);
   const int64_t N = out.size(1);
   const int64_t PM = out.size(0);
@@ -1106,20 +1101,10 @@ void moe_gemm_mxfp4_mxfp8(at::Tensor out, at::Tensor a_q, at::Tensor a_scale,
                   (N + 63) / 64 <= 65535,
               "moe_gemm_mxfp4_mxfp8: need K % 128 == 0 and N % 16 == 0 "
               "(N % 32 == 0 with gate_up)");
-  TORCH_CHECK(PM >= BM && PM % BM == 0 && PM < (1LL << 31),
-              "moe_gemm_mxfp4_mxfp8: padded rows must be a positive multiple "
-              "of block_m");
-  TORCH_CHECK(w_packed.size(0) >= 1 && w_packed.size(1) == NB &&
-                  w_packed.size(2) == K / 2 &&
-                  w_scale.size(0) == w_packed.size(0) &&
-                  w_scale.size(1) == NB && w_scale.size(2) == K / 32,
-              "moe_gemm_mxfp4_mxfp8: need w_packed [E, NB, K/2] and w_scale "
-              "[E, NB, K/32]");
-  TORCH_CHECK(expert_ids.numel() >= PM / BM && sorted_ids.numel() >= PM &&
-                  a_q.size(0) >= 1 && (gate_up || a_q.size(0) >= PM) &&
-                  a_scale.size(0) == a_q.size(0) && a_scale.size(1) == K / 32,
-              "moe_gemm_mxfp4_mxfp8: sorted_ids / expert_ids / a_q too short "
-              "or a_scale not [rows, K/32]");
+  check_moe_mxfp4("moe_gemm_mxfp4_mxfp8", out, w_packed, w_scale, sorted_ids,
+                  expert_ids, n_valid, K, NB, BM);
+  TORCH_CHECK(a_q.size(0) >= 1 && (gate_up || a_q.size(0) >= PM),
+              "moe_gemm_mxfp4_mxfp8: a_q too short");
   unsigned char* out_scale_p = nullptr;
   if (gate_up) {
     TORCH_CHECK(out_scale.has_value() && out_scale->is_cuda() &&
@@ -1136,17 +1121,10 @@ void moe_gemm_mxfp4_mxfp8(at::Tensor out, at::Tensor a_q, at::Tensor a_scale,
   }
   TORCH_CHECK(reinterpret_cast<uintptr_t>(a_q.data_ptr()) % 16 == 0 &&
                   reinterpret_cast<uintptr_t>(a_scale.data_ptr()) % 4 == 0 &&
-                  reinterpret_cast<uintptr_t>(w_packed.data_ptr()) % 16 == 0 &&
                   reinterpret_cast<uintptr_t>(out.data_ptr()) % 8 == 0,
-              "moe_gemm_mxfp4_mxfp8: a_q and w_packed must be 16-byte, out "
-              "8-byte and a_scale 4-byte aligned");
-  const auto dev = out.get_device();
-  TORCH_CHECK(a_q.get_device() == dev && a_scale.get_device() == dev &&
-                  w_packed.get_device() == dev &&
-                  w_scale.get_device() == dev &&
-                  sorted_ids.get_device() == dev &&
-                  expert_ids.get_device() == dev &&
-                  n_valid.get_device() == dev,
+              "moe_gemm_mxfp4_mxfp8: a_q must be 16-byte, out 8-byte and "
+              "a_scale 4-byte aligned");
+  TORCH_CHECK(a_q.get_device() == out.get_device(),
               "moe_gemm_mxfp4_mxfp8: tensors must share one device");
   fi::launch_moe_gemm_mxfp4_mxfp8(
       out.data_ptr(), out_scale_p,

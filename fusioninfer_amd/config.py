@@ -35,7 +35,8 @@ class ModelConfig:
     dtype: str = "bfloat16"
     # optional HF-layout safetensors checkpoint dir; None = random init
     model_path: Optional[str] = None
-    # None = bf16; "fp8" = OCP e4m3 weights + dynamic per-token activations
+    # None = bf16; "fp8" = OCP e4m3 weights + dynamic per-token activations;
+    # "mxfp4" / "int4" = 4-bit weight-only (W4A16)
     quantization: Optional[str] = None
     # with quantization == "mxfp4": store the MoE experts as MXFP4 too and
     # run them on the grouped W4A16 GEMM. Off: an MoE model is refused in
@@ -55,6 +56,11 @@ class ModelConfig:
     # (models/model.py: MXFP4_MOE_WIDE_LO / _HI). Smaller batches (decode) are
     # the same in all three.
     mxfp4_moe_activations: str = "bf16"
+    # with quantization == "int4" (AWQ / GPTQ style: unsigned 4-bit codes,
+    # one fp16 scale and one zero point per group): input channels per
+    # group, 32, 64 or 128. A pre-quantised checkpoint sets it from its
+    # quantization_config. Dense models only.
+    int4_group_size: int = 128
     # MoE (Qwen3-MoE family): num_experts 0 = dense MLP
     num_experts: int = 0
     num_experts_per_tok: int = 8

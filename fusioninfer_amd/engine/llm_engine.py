@@ -174,6 +174,9 @@ class LLMEngine:
         assert self.cfg.model.quantization != "mxfp4", (
             "LoRA is not supported with --quantization mxfp4"
         )
+        assert self.cfg.model.quantization != "int4", (
+            "LoRA is not supported with --quantization int4"
+        )
         if (self.cfg.parallel.tensor_parallel_size
                 * self.cfg.parallel.pipeline_parallel_size) > 1:
             assert self.is_driver

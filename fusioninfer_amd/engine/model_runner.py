@@ -66,10 +66,33 @@ class ModelRunner:
             # stay bf16: refuse rather than mislead (mxfp4_moe_experts
             # converts them too; opt-in)
             raise ValueError("mxfp4 does not cover MoE experts yet")
+        if mc.quantization == "int4":
+            if mc.is_moe:
+                raise ValueError("int4 does not cover MoE experts")
+            if mc.int4_group_size not in (32, 64, 128):
+                raise ValueError(
+                    "int4_group_size must be 32, 64 or 128, got "
+                    f"{mc.int4_group_size!r}")
         fp8_ckpt = False
+        int4_ckpt = None  # "awq" / "gptq" for a pre-quantised checkpoint
         if mc.model_path:
-            from fusioninfer_amd.models.weight_loader import checkpoint_is_fp8
+            from fusioninfer_amd.models.weight_loader import (
+                checkpoint_int4_config,
+                checkpoint_is_fp8,
+            )
 
+            int4_cfg = checkpoint_int4_config(mc.model_path)
+            if int4_cfg is not None:
+                # an AWQ / GPTQ checkpoint implies int4 serving at its own
+                # group size
+                if mc.quantization not in (None, "int4"):
+                    raise ValueError(
+                        f"the checkpoint is {int4_cfg[0]} 4-bit; it cannot "
+                        f"be served with quantization={mc.quantization!r}")
+                if mc.is_moe:
+                    raise ValueError("int4 does not cover MoE experts")
+                int4_ckpt, mc.int4_group_size = int4_cfg
+                mc.quantization = "int4"
             fp8_ckpt = checkpoint_is_fp8(mc.model_path)
             if fp8_ckpt and mc.quantization is None:
                 # fp8-native checkpoint implies fp8 serving (vLLM
@@ -85,6 +108,15 @@ class ModelRunner:
 
             assert convert_linear_to_fp8(self.model) > 0
             load_safetensors_dir(self.model, mc.model_path)
+        elif int4_ckpt is not None:
+            # pre-quantised checkpoint: make the int4 buffers first, then
+            # the loader converts qweight / qzeros / scales into them
+            from fusioninfer_amd.models.weight_loader import load_safetensors_dir
+            from fusioninfer_amd.quantization import convert_linear_to_int4
+
+            assert convert_linear_to_int4(
+                self.model, mc.int4_group_size, quantize=False) > 0
+            load_safetensors_dir(self.model, mc.model_path, int4_ckpt)
         else:
             if mc.model_path:
                 from fusioninfer_amd.models.weight_loader import (
@@ -118,7 +150,16 @@ class ModelRunner:
                     # the KV cache is sized
                     assert convert_moe_experts_to_mxfp4(
                         self.model, mc.mxfp4_moe_activations) > 0
-        if mc.quantization not in (None, "fp8", "mxfp4"):
+            elif mc.quantization == "int4":
+                # weight-only: bf16 weights (checkpoint or random init) are
+                # quantised here, per group of int4_group_size
+                from fusioninfer_amd.quantization import (
+                    convert_linear_to_int4,
+                )
+
+                assert convert_linear_to_int4(
+                    self.model, mc.int4_group_size) > 0
+        if mc.quantization not in (None, "fp8", "mxfp4", "int4"):
             raise ValueError(f"unknown quantization {mc.quantization!r}")
         spec = getattr(cfg, "speculative", None)
         verify_attention = spec.verify_attention if spec else "prefill"
@@ -154,7 +195,7 @@ class ModelRunner:
         self.num_lora_eager_steps = 0    # decode steps with adapters run eager
         self.num_lora_slot_steps = 0     # steps (any kind) on the slot kernels
         self.num_lora_loop_steps = 0     # steps on the per-adapter torch loop
-        if cfg.enable_lora and mc.quantization not in ("fp8", "mxfp4"):
+        if cfg.enable_lora and mc.quantization not in ("fp8", "mxfp4", "int4"):
             from fusioninfer_amd.lora import LoRASlots
 
             self.lora_slots = LoRASlots(

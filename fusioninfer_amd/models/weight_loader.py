@@ -12,8 +12,9 @@ be able to load real weights. This maps HuggingFace parameter names
 
 from __future__ import annotations
 
+import json
 import os
-from typing import Dict, Iterable, Tuple
+from typing import Dict, Iterable, Optional, Tuple
 
 import torch
 
@@ -57,10 +58,109 @@ def checkpoint_is_fp8(path: str) -> bool:
     return False
 
 
+def int4_quantization_config(qc) -> Optional[Tuple[str, int]]:
+    """(method, group_size) of an AWQ or GPTQ 4-bit `quantization_config`
+    (the dict of a HF config.json), or None when it describes neither.
+    A checkpoint the int4 path cannot serve raises ValueError naming the
+    field: bits != 4, desc_act (act-order), a group size outside
+    {32, 64, 128}, an AWQ version other than gemm or zero_point false (other
+    tensor layouts), a GPTQ checkpoint_format other than gptq (v2 stores the
+    zero points unshifted)."""
+    if not qc:
+        return None
+    method = str(qc.get("quant_method", "")).lower()
+    if method not in ("awq", "gptq"):
+        return None
+    bits = qc.get("bits", qc.get("w_bit"))
+    if bits != 4:
+        raise ValueError(
+            f"{method} checkpoint: quantization_config.bits is {bits!r}; "
+            "only 4-bit weights are supported")
+    if qc.get("desc_act", False):
+        raise ValueError(
+            f"{method} checkpoint: quantization_config.desc_act is true; "
+            "act-order checkpoints are not supported")
+    group_size = qc.get("group_size", qc.get("q_group_size"))
+    if group_size not in (32, 64, 128):
+        raise ValueError(
+            f"{method} checkpoint: quantization_config.group_size is "
+            f"{group_size!r}; supported group sizes are 32, 64 and 128")
+    for field, want in (("version", "gemm"), ("zero_point", True)) \
+            if method == "awq" else (("checkpoint_format", "gptq"),):
+        got = qc.get(field, want)
+        if (got.lower() if isinstance(got, str) else got) != want:
+            raise ValueError(
+                f"{method} checkpoint: quantization_config.{field} is "
+                f"{got!r}; only {want!r} is supported")
+    return method, int(group_size)
+
+
+def checkpoint_int4_config(path: str) -> Optional[Tuple[str, int]]:
+    """int4_quantization_config of the checkpoint directory's config.json;
+    None when there is no such file or no quantization_config in it."""
+    cfg_path = os.path.join(path, "config.json")
+    if not os.path.exists(cfg_path):
+        return None
+    with open(cfg_path) as f:
+        return int4_quantization_config(
+            json.load(f).get("quantization_config"))
+
+
+_INT4_KINDS = ("qweight", "qzeros", "scales")
+_INT4_PROJ = {
+    "self_attn.q_proj": "q", "self_attn.k_proj": "k", "self_attn.v_proj": "v",
+    "self_attn.o_proj": "o", "mlp.gate_proj": "gate", "mlp.up_proj": "up",
+    "mlp.down_proj": "down",
+}
+
+
+def _load_int4_layer(layer, staged, method: str, tp: int, rank: int) -> None:
+    """Convert the staged AWQ / GPTQ tensors of one decoder layer and copy
+    them into its int4 buffers (quantization.convert_linear_to_int4 with
+    quantize=False made them). q/k/v and gate/up merge by rows; column-
+    parallel shards slice rows, row-parallel shards slice K, of all three
+    tensors alike."""
+    from fusioninfer_amd.ops import validate_int4_scales
+    from fusioninfer_amd.quantization import int4_from_awq, int4_from_gptq
+
+    def convert(proj):
+        t = [staged[(proj, kind)] for kind in _INT4_KINDS]
+        return int4_from_awq(*t) if method == "awq" else int4_from_gptq(*t)
+
+    def store(module, parts):
+        parts = [torch.cat(p, dim=0) for p in zip(*parts)]
+        validate_int4_scales(parts[1], parts[2])
+        for buf, v in zip((module.weight_packed, module.weight_scale,
+                           module.weight_zero), parts):
+            if buf.shape != v.shape:
+                raise ValueError(
+                    f"{method} checkpoint: shard {tuple(v.shape)} does not "
+                    f"fit the model's {tuple(buf.shape)} (group size "
+                    f"{module.int4_group_size})")
+            buf.copy_(v)
+
+    def rows(proj):
+        return tuple(_shard_rows(t, tp, rank) for t in convert(proj))
+
+    def cols(proj):
+        return tuple(_shard_cols(t, tp, rank) for t in convert(proj))
+
+    store(layer.self_attn.qkv_proj, [rows("q"), rows("k"), rows("v")])
+    store(layer.self_attn.o_proj, [cols("o")])
+    store(layer.mlp.gate_up_proj, [rows("gate"), rows("up")])
+    store(layer.mlp.down_proj, [cols("down")])
+
+
 def load_hf_state_dict(
-    model, tensors: Iterable[Tuple[str, torch.Tensor]]
+    model, tensors: Iterable[Tuple[str, torch.Tensor]],
+    int4_method: Optional[str] = None,
 ) -> int:
-    """Load HF-named tensors into a CausalLM. Returns #tensors consumed."""
+    """Load HF-named tensors into a CausalLM. Returns #tensors consumed.
+    `int4_method` ("awq" or "gptq") names the layout of the qweight /
+    qzeros / scales tensors of a pre-quantised 4-bit checkpoint; the model's
+    projections must already be int4 (convert_linear_to_int4)."""
+    from fusioninfer_amd.quantization import check_trivial_g_idx
+
     cfg = model.cfg
     tp = ps.tp_world_size()
     rank = ps.tp_rank()
@@ -70,6 +170,10 @@ def load_hf_state_dict(
     # staging for fused weights: (layer, which) -> tensor
     pending: Dict[Tuple[int, str], torch.Tensor] = {}
     moe_pending: Dict[Tuple[int, int, str], torch.Tensor] = {}
+    # pre-quantised 4-bit tensors: layer -> (projection, kind) -> tensor. A
+    # layer is converted and dropped as soon as its 21 tensors are here
+    int4_staged: Dict[int, Dict[Tuple[str, str], torch.Tensor]] = {}
+    int4_done = set()
     loaded = 0
 
     def put(param: torch.nn.Parameter, value: torch.Tensor):
@@ -223,7 +327,23 @@ def load_hf_state_dict(
                 continue
             rest = ".".join(parts[3:])
             layer = local(li)
-            if rest == "self_attn.q_proj.weight":
+            proj, _, kind = rest.rpartition(".")
+            if proj in _INT4_PROJ and kind in _INT4_KINDS + ("g_idx",):
+                if int4_method is None:
+                    raise ValueError(
+                        f"{name}: a pre-quantised 4-bit tensor, but no "
+                        "int4_method (awq / gptq) was given")
+                if kind == "g_idx":  # only the trivial k // G is accepted
+                    check_trivial_g_idx(
+                        w, layer.mlp.down_proj.int4_group_size, name)
+                    continue
+                staged = int4_staged.setdefault(li, {})
+                staged[(_INT4_PROJ[proj], kind)] = w
+                if len(staged) == len(_INT4_PROJ) * len(_INT4_KINDS):
+                    _load_int4_layer(layer, int4_staged.pop(li), int4_method,
+                                     tp, rank)
+                    int4_done.add(li)
+            elif rest == "self_attn.q_proj.weight":
                 pending[(li, "q")] = w
                 try_fuse_qkv(li)
             elif rest == "self_attn.k_proj.weight":
@@ -305,6 +425,15 @@ def load_hf_state_dict(
                 loaded -= 1  # unknown (bias-less models shouldn't hit this)
         else:
             loaded -= 1
+    if int4_method is not None:
+        # a layer left on the buffers convert_linear_to_int4 allocated would
+        # serve zeros without a word
+        missing = sorted(set(range(model.layer_start, model.layer_end))
+                         - int4_done)
+        if missing:
+            raise ValueError(
+                f"{int4_method} checkpoint: layers {missing} lack qweight / "
+                "qzeros / scales of some projection")
     assert not pending, f"unfused partial weights remain: {list(pending)}"
     assert not moe_pending, (
         f"unfused expert weights remain: {list(moe_pending)[:4]}"
@@ -317,7 +446,8 @@ def load_hf_state_dict(
     return loaded
 
 
-def load_safetensors_dir(model, path: str) -> int:
+def load_safetensors_dir(model, path: str,
+                         int4_method: Optional[str] = None) -> int:
     """Load all *.safetensors under `path` (HF checkpoint directory)."""
     from safetensors.torch import safe_open
 
@@ -334,7 +464,7 @@ def load_safetensors_dir(model, path: str) -> int:
                 for name in sf.keys():
                     yield name, sf.get_tensor(name)
 
-    return load_hf_state_dict(model, tensor_iter())
+    return load_hf_state_dict(model, tensor_iter(), int4_method)
 
 
 def export_hf_state_dict(model) -> Dict[str, torch.Tensor]:

@@ -737,7 +737,7 @@ def _check_mxfp4_weight(op: str, w_packed, w_scale):
     return N, K
 
 
-def _check_mxfp4_out(op: str, out, shape, device):
+def _check_bf16_out(op: str, out, shape, device):
     if (out.dtype != torch.bfloat16 or tuple(out.shape) != shape
             or out.device != device or not out.is_contiguous()):
         raise ValueError(
@@ -774,7 +774,7 @@ def mxfp4_linear(x, w_packed, w_scale, bias=None, out=None):
             f"{x.device}")
     M = x.shape[0]
     if out is not None:
-        _check_mxfp4_out("mxfp4_linear", out, (M, N), x.device)
+        _check_bf16_out("mxfp4_linear", out, (M, N), x.device)
     if x.is_cuda:
         _require_native()
         if out is None:
@@ -794,7 +794,7 @@ def mxfp4_dequant(w_packed, w_scale, out=None):
     Same weight contract as mxfp4_linear."""
     N, K = _check_mxfp4_weight("mxfp4_dequant", w_packed, w_scale)
     if out is not None:
-        _check_mxfp4_out("mxfp4_dequant", out, (N, K), w_packed.device)
+        _check_bf16_out("mxfp4_dequant", out, (N, K), w_packed.device)
     if w_packed.is_cuda:
         _require_native()
         if out is None:
@@ -803,6 +803,137 @@ def mxfp4_dequant(w_packed, w_scale, out=None):
         _C.mxfp4_dequant(out, w_packed, w_scale)
         return out
     res = ref.mxfp4_dequant(w_packed, w_scale)
+    if out is None:
+        return res
+    out.copy_(res)
+    return out
+
+
+# ----------------------------------------------------------------- int4
+
+INT4_GROUP_SIZES = (32, 64, 128)
+_FP16_MIN_NORMAL = 2.0 ** -14
+
+
+def validate_int4_scales(w_scale: torch.Tensor, w_zero: torch.Tensor) -> None:
+    """Raise ValueError on a scale that is not a finite, positive, normal
+    fp16, or a zero point above 15. Reads the tensors on the host
+    (synchronises on GPU tensors): call it when weights are converted or
+    loaded, never per forward. The compute ops do not scan them; feeding
+    them a value this rejects is outside their contract."""
+    if w_scale.dtype != torch.float16:
+        raise ValueError(
+            f"int4: weight_scale must be float16, got {w_scale.dtype}")
+    if w_zero.dtype != torch.uint8:
+        raise ValueError(
+            f"int4: weight_zero must be uint8, got {w_zero.dtype}")
+    if w_scale.numel() > 0:
+        s = w_scale.float()
+        # a NaN fails the first comparison, an infinity the second
+        if not bool(((s >= _FP16_MIN_NORMAL) & (s <= 65504.0)).all()):
+            raise ValueError(
+                "int4: every scale must be a finite, positive, normal fp16 "
+                f"(in [2^-14, 65504]); got values spanning "
+                f"[{float(s.min())}, {float(s.max())}]")
+    if w_zero.numel() > 0 and int(w_zero.max()) > 15:
+        raise ValueError(
+            f"int4: zero points must be at most 15, got {int(w_zero.max())}")
+
+
+def _check_int4_weight(op: str, w_packed, w_scale, w_zero, group_size):
+    if group_size not in INT4_GROUP_SIZES:
+        raise ValueError(
+            f"{op}: group_size must be one of {INT4_GROUP_SIZES}, got "
+            f"{group_size!r}")
+    if (w_packed.dtype != torch.uint8 or w_scale.dtype != torch.float16
+            or w_zero.dtype != torch.uint8):
+        raise ValueError(
+            f"{op}: weight_packed and weight_zero must be uint8 and "
+            f"weight_scale float16, got {w_packed.dtype}, {w_zero.dtype} and "
+            f"{w_scale.dtype}")
+    if w_packed.dim() != 2 or w_scale.dim() != 2 or w_zero.dim() != 2:
+        raise ValueError(f"{op}: the weight tensors must be 2-D")
+    N, K = w_packed.shape[0], w_packed.shape[1] * 2
+    if K < 128 or K % 128 != 0 or N < 16 or N % 16 != 0:
+        raise ValueError(
+            f"{op}: unsupported shape N={N} K={K} "
+            "(need K % 128 == 0 and N % 16 == 0)")
+    want = (N, K // group_size)
+    if tuple(w_scale.shape) != want or tuple(w_zero.shape) != want:
+        raise ValueError(
+            f"{op}: weight_scale and weight_zero must be [N, K/group_size] = "
+            f"{want}, got {tuple(w_scale.shape)} and {tuple(w_zero.shape)}")
+    if w_scale.device != w_packed.device or w_zero.device != w_packed.device:
+        raise ValueError(f"{op}: weight tensors must share one device")
+    if not (w_packed.is_contiguous() and w_scale.is_contiguous()
+            and w_zero.is_contiguous()):
+        raise ValueError(f"{op}: weight tensors must be contiguous")
+    return N, K
+
+
+def int4_linear(x, w_packed, w_scale, w_zero, group_size, bias=None, out=None):
+    """W4A16 linear on int4 group-quantised weights (AWQ / GPTQ format):
+
+        out[m, n] = bf16( sum_k x[m, k] * dq(W)[n, k] (+ bias[n]) )
+        dq(W)[n, k] = bf16_rne( fp32(q - z) * fp32(s) )
+
+    with fp32 accumulation and one rounding of the sum. x [M, K] bf16
+    contiguous, w_packed [N, K/2] uint8 (k even in the low nibble), w_scale
+    [N, K/G] fp16 and w_zero [N, K/G] uint8 (see validate_int4_scales),
+    G = group_size in {32, 64, 128}, bias [N] bf16 or None. K % 128 == 0,
+    N % 16 == 0, any M >= 0. Static grid, no host sync, no workspace:
+    hipGraph-capturable. A row's bits depend only on that x row and the
+    weights (deterministic, batch-invariant). Unsupported input raises
+    ValueError (no silent fallback)."""
+    N, K = _check_int4_weight("int4_linear", w_packed, w_scale, w_zero,
+                              group_size)
+    if x.dtype != torch.bfloat16:
+        raise ValueError(f"int4_linear: x must be bf16, got {x.dtype}")
+    if x.dim() != 2 or x.shape[1] != K:
+        raise ValueError(
+            f"int4_linear: x must be [M, {K}], got {tuple(x.shape)}")
+    if not x.is_contiguous():
+        raise ValueError("int4_linear: x must be contiguous")
+    if x.device != w_packed.device:
+        raise ValueError("int4_linear: x and the weights must share one device")
+    if bias is not None and (
+            bias.dtype != torch.bfloat16 or tuple(bias.shape) != (N,)
+            or bias.device != x.device or not bias.is_contiguous()):
+        raise ValueError(
+            f"int4_linear: bias must be a contiguous bf16 [{N}] tensor on "
+            f"{x.device}")
+    M = x.shape[0]
+    if out is not None:
+        _check_bf16_out("int4_linear", out, (M, N), x.device)
+    if x.is_cuda:
+        _require_native()
+        if out is None:
+            out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+        if M > 0:
+            _C.int4_linear(out, x, w_packed, w_scale, w_zero, group_size, bias)
+        return out
+    res = ref.int4_linear(x, w_packed, w_scale, w_zero, group_size, bias)
+    if out is None:
+        return res
+    out.copy_(res)
+    return out
+
+
+def int4_dequant(w_packed, w_scale, w_zero, group_size, out=None):
+    """Expand int4 group-quantised weights to bf16 [N, K], bit for bit the
+    dq of int4_linear. Same weight contract as int4_linear."""
+    N, K = _check_int4_weight("int4_dequant", w_packed, w_scale, w_zero,
+                              group_size)
+    if out is not None:
+        _check_bf16_out("int4_dequant", out, (N, K), w_packed.device)
+    if w_packed.is_cuda:
+        _require_native()
+        if out is None:
+            out = torch.empty((N, K), dtype=torch.bfloat16,
+                              device=w_packed.device)
+        _C.int4_dequant(out, w_packed, w_scale, w_zero, group_size)
+        return out
+    res = ref.int4_dequant(w_packed, w_scale, w_zero, group_size)
     if out is None:
         return res
     out.copy_(res)
@@ -890,7 +1021,7 @@ def mxfp4_mxfp8_linear(x_q, x_scale, w_packed, w_scale, bias=None, out=None):
             f"{op}: bias must be a contiguous bf16 [{N}] tensor on "
             f"{x_q.device}")
     if out is not None:
-        _check_mxfp4_out(op, out, (M, N), x_q.device)
+        _check_bf16_out(op, out, (M, N), x_q.device)
     if x_q.is_cuda:
         _require_native()
         if out is None:

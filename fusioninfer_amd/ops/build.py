@@ -37,6 +37,7 @@ SOURCES = [
     "mxfp8_gemm.hip",
     "moe_mxfp4_gemm.hip",
     "moe_mxfp8_gemm.hip",
+    "int4_gemm.hip",
 ]
 
 

@@ -76,6 +76,11 @@ void launch_moe_gemm_mxfp4_mxfp8(void*, unsigned char*, const unsigned char*,
                                  const unsigned char*, const int*, const int*,
                                  const int*, int, int, int, bool, int,
                                  hipStream_t);
+void launch_int4_linear(u16*, const u16*, const unsigned char*, const u16*,
+                        const unsigned char*, const u16*, int, int, int, int,
+                        hipStream_t);
+void launch_int4_dequant(u16*, const unsigned char*, const u16*,
+                         const unsigned char*, int64_t, int, hipStream_t);
 void launch_sample_tokens(int64_t*, const float*, const float*, const int*,
                           const float*, const float*, const int64_t*, int,
                           int, hipStream_t);
@@ -908,6 +913,100 @@ void mxfp4_dequant(at::Tensor out, at::Tensor w_packed, at::Tensor w_scale) {
       current_stream());
 }
 
+// shared checks of the int4 ops: weight_packed [N, K/2] uint8, weight_scale
+// [N, K/G] fp16 and weight_zero [N, K/G] uint8, contiguous on one GPU;
+// returns log2(G / 32)
+int check_int4_weight(const at::Tensor& w_packed, const at::Tensor& w_scale,
+                      const at::Tensor& w_zero, int64_t group_size,
+                      int64_t* N, int64_t* K) {
+  TORCH_CHECK(w_packed.is_cuda() && w_scale.is_cuda() && w_zero.is_cuda(),
+              "int4: weights must be on GPU");
+  TORCH_CHECK(w_packed.scalar_type() == at::kByte &&
+                  w_scale.scalar_type() == at::kHalf &&
+                  w_zero.scalar_type() == at::kByte,
+              "int4: weight_packed and weight_zero must be uint8 and "
+              "weight_scale float16");
+  TORCH_CHECK(w_packed.dim() == 2 && w_scale.dim() == 2 && w_zero.dim() == 2 &&
+                  w_packed.is_contiguous() && w_scale.is_contiguous() &&
+                  w_zero.is_contiguous(),
+              "int4: weights must be 2-D and contiguous");
+  TORCH_CHECK(group_size == 32 || group_size == 64 || group_size == 128,
+              "int4: group_size must be 32, 64 or 128");
+  *N = w_packed.size(0);
+  *K = w_packed.size(1) * 2;
+  TORCH_CHECK(*N >= 16 && *N % 16 == 0 && *K >= 128 && *K % 128 == 0 &&
+                  *N < (1LL << 31) && *K < (1LL << 31),
+              "int4: need K % 128 == 0 and N % 16 == 0");
+  TORCH_CHECK(w_scale.size(0) == *N && w_scale.size(1) == *K / group_size &&
+                  w_zero.size(0) == *N && w_zero.size(1) == *K / group_size,
+              "int4: weight_scale and weight_zero must be [N, K/group_size]");
+  TORCH_CHECK(w_packed.get_device() == w_scale.get_device() &&
+                  w_packed.get_device() == w_zero.get_device(),
+              "int4: weight tensors must share one device");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(w_packed.data_ptr()) % 16 == 0,
+              "int4: weight_packed must be 16-byte aligned");
+  return group_size == 32 ? 0 : group_size == 64 ? 1 : 2;
+}
+
+void int4_linear(at::Tensor out, at::Tensor x, at::Tensor w_packed,
+                 at::Tensor w_scale, at::Tensor w_zero, int64_t group_size,
+                 c10::optional<at::Tensor> bias) {
+  CHECK_BF16_CUDA(out);
+  CHECK_BF16_CUDA(x);
+  int64_t N, K;
+  const int gshift =
+      check_int4_weight(w_packed, w_scale, w_zero, group_size, &N, &K);
+  TORCH_CHECK(x.dim() == 2 && out.dim() == 2 && x.is_contiguous() &&
+                  out.is_contiguous(),
+              "int4_linear: x and out must be 2-D and contiguous");
+  const int64_t M = x.size(0);
+  TORCH_CHECK(M >= 1 && M <= 65535 * 16 && x.size(1) == K &&
+                  out.size(0) == M && out.size(1) == N,
+              "int4_linear: need x [M, K], out [M, N], 1 <= M <= 1048560");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "int4_linear: x must be 16-byte aligned");
+  TORCH_CHECK(x.get_device() == out.get_device() &&
+                  x.get_device() == w_packed.get_device(),
+              "int4_linear: tensors must share one device");
+  const u16* bias_p = nullptr;
+  if (bias.has_value()) {
+    CHECK_BF16_CUDA(*bias);
+    TORCH_CHECK(bias->dim() == 1 && bias->numel() == N &&
+                    bias->is_contiguous() &&
+                    bias->get_device() == x.get_device(),
+                "int4_linear: bias must be a contiguous [N] bf16 tensor");
+    bias_p = bf16_cptr(*bias);
+  }
+  fi::launch_int4_linear(
+      bf16_ptr(out), bf16_cptr(x),
+      static_cast<const unsigned char*>(w_packed.data_ptr()),
+      static_cast<const u16*>(w_scale.data_ptr()),
+      static_cast<const unsigned char*>(w_zero.data_ptr()), bias_p,
+      static_cast<int>(M), static_cast<int>(N), static_cast<int>(K), gshift,
+      current_stream());
+}
+
+void int4_dequant(at::Tensor out, at::Tensor w_packed, at::Tensor w_scale,
+                  at::Tensor w_zero, int64_t group_size) {
+  CHECK_BF16_CUDA(out);
+  int64_t N, K;
+  const int gshift =
+      check_int4_weight(w_packed, w_scale, w_zero, group_size, &N, &K);
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == N && out.size(1) == K &&
+                  out.is_contiguous() &&
+                  out.get_device() == w_packed.get_device(),
+              "int4_dequant: out must be a contiguous [N, K] bf16 tensor");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(out.data_ptr()) % 16 == 0,
+              "int4_dequant: out must be 16-byte aligned");
+  const int64_t nruns = N * (K / 32);
+  TORCH_CHECK(nruns / 256 < (1LL << 31) - 1, "int4_dequant: too large");
+  fi::launch_int4_dequant(
+      bf16_ptr(out), static_cast<const unsigned char*>(w_packed.data_ptr()),
+      static_cast<const u16*>(w_scale.data_ptr()),
+      static_cast<const unsigned char*>(w_zero.data_ptr()), nruns, gshift,
+      current_stream());
+}
+
 // shared checks of the ops on MXFP8 rows: q [rows, K] e4m3 and scale
 // [rows, K/32] uint8, both contiguous on one GPU
 void check_mxfp8_rows(const char* op, const at::Tensor& q,
@@ -1449,6 +1548,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mxfp4_linear", &mxfp4_linear,
         "W4A16 linear on MXFP4 weights (bf16 in/out, fp32 accumulation)");
   m.def("mxfp4_dequant", &mxfp4_dequant, "expand MXFP4 weights to bf16");
+  m.def("int4_linear", &int4_linear,
+        "W4A16 linear on int4 group-quantised weights (fp16 scale and zero "
+        "point per group; bf16 in/out, fp32 accumulation)");
+  m.def("int4_dequant", &int4_dequant,
+        "expand int4 group-quantised weights to bf16");
   m.def("quant_mxfp8_rows", &quant_mxfp8_rows,
         "bf16 rows -> MXFP8 (e4m3 elements, one e8m0 scale per 32 k)");
   m.def("mxfp4_mxfp8_linear", &mxfp4_mxfp8_linear,

@@ -734,6 +734,31 @@ def mxfp4_linear(x, w_packed, w_scale, bias=None) -> torch.Tensor:
     return out.to(torch.bfloat16)
 
 
+def int4_dequant(w_packed, w_scale, w_zero, group_size: int) -> torch.Tensor:
+    """Int4 group-quantised weights -> bf16 [N, K]:
+    dq[n, k] = bf16_rne(fp32(q - z) * fp32(s)). w_packed [N, K/2] uint8 holds
+    code q of k = 2j in the low nibble of byte j and k = 2j + 1 in the high
+    nibble; w_scale [N, K/G] fp16 and w_zero [N, K/G] uint8 (0..15) belong to
+    each group of G consecutive k. The fp32 product is exact (5 x 11 bits),
+    so the bf16 conversion is the only rounding."""
+    N, half = w_packed.shape
+    codes = torch.stack((w_packed & 0xF, w_packed >> 4), dim=-1).reshape(N, -1)
+    diff = (codes.view(N, -1, group_size).to(torch.int32)
+            - w_zero.to(torch.int32).unsqueeze(-1)).float()
+    out = diff * w_scale.float().unsqueeze(-1)
+    return out.view(N, 2 * half).to(torch.bfloat16)
+
+
+def int4_linear(x, w_packed, w_scale, w_zero, group_size: int,
+                bias=None) -> torch.Tensor:
+    """x [M, K] bf16 @ dq(W)^T (+ bias) in fp32, rounded to bf16 once."""
+    out = (x.float()
+           @ int4_dequant(w_packed, w_scale, w_zero, group_size).float().t())
+    if bias is not None:
+        out = out + bias.float()
+    return out.to(torch.bfloat16)
+
+
 def mxfp8_quant_rows(x: torch.Tensor):
     """bf16 [M, K] -> (e4m3 [M, K], e8m0 uint8 [M, K/32]): MXFP8 along K.
     Per 32-k block: amax in fp32; s = 127 for an all-zero block, else

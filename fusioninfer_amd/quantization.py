@@ -1,4 +1,4 @@
-"""Quantized linear paths: FP8 (OCP e4m3, W8A8) and MXFP4 (W4A16, below).
+"""Quantized linear paths: FP8 (OCP e4m3, W8A8), MXFP4 and int4 (W4A16, below).
 
 gfx950 runs OCP fp8 MFMA at ~2x the bf16 rate and halves weight-read
 bytes — decode-time GEMMs are weight-bandwidth-bound, so fp8 weights pay
@@ -21,6 +21,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from fusioninfer_amd.distributed import parallel_state as ps
+from fusioninfer_amd.ops import INT4_GROUP_SIZES, validate_int4_scales
 
 FP8_DTYPE = torch.float8_e4m3fn
 FP8_MAX = 448.0  # e4m3fn max normal
@@ -331,6 +332,259 @@ def _make_mxfp4_forward(m, scratch, activations="bf16"):
             out = F.linear(x, w, bias)
         else:
             out = ops.mxfp4_linear(x, m.weight_packed, m.weight_scale, bias)
+        if is_row_parallel:
+            out = ps.tp_all_reduce(out)
+        return out
+
+    return fwd
+
+
+# ------------------------------------------------------------------- int4
+#
+# Weight-only 4-bit mode for AWQ / GPTQ style weights (`--quantization
+# int4`): unsigned 4-bit codes q along K, two per byte with k even in the low
+# nibble (the MXFP4 nibble convention, so shards concatenate and slice the
+# same way), and per group of G = 32, 64 or 128 consecutive k of an output
+# row one fp16 scale s and one zero point z in 0..15:
+#
+#     dq(W)[n, k] = bf16_rne( fp32(q - z) * fp32(s) )
+#
+# The fp32 product is exact, so dq has exactly one rounding, and the W4A16
+# GEMM is "a bf16 GEMM with fp32 accumulation on dq(W)". Scales stay fp16
+# because checkpoints store fp16. 4 + 24 / G bits per weight.
+
+# Largest M served by the weight-streaming HIP GEMM (ops.int4_linear);
+# larger batches expand the weight into the shared bf16 scratch and call the
+# library GEMM. Measured on the Qwen3-8B shapes (profiles/r19_int4.md): it
+# beats dequant + F.linear on all four in every repetition up to M = 16; at
+# M = 32 it loses on down_proj (K = 12288: 71 us against 57 us), where the
+# M <= 32 instance fills only 64 workgroups. mxfp4's threshold is 32: the
+# integer expansion costs 18 VALU per 8 codes against 4 converts.
+INT4_MAX_M = int(os.environ.get("FI_INT4_MAX_M", "16"))
+
+
+def quantize_weight_int4(w: torch.Tensor, group_size: int = 128):
+    """[N, K] -> (packed [N, K/2] uint8, scale [N, K/G] fp16, zero [N, K/G]
+    uint8): asymmetric, per group of G consecutive k, all in fp32:
+
+        wmin = min(group, 0), wmax = max(group, 0)
+        s = fp16(max(wmax - wmin, tiny) / 15), clamped to fp16's normal range
+            [2^-14, 65504], with tiny = 15 * 2^-14
+        z = clamp(round(-wmin / s), 0, 15)
+        q = clamp(round(w / s) + z, 0, 15)
+
+    where s in the last two lines is the stored fp16 value and round is to
+    nearest, ties to even. The range is widened to contain 0, so a group of
+    one sign (a constant group included) is covered by the grid instead of
+    saturating, and 0 itself is always exact (q == z). Within a group
+    |w - dq| <= s / 2, plus 15 s 2^-11 for the fp16 rounding of s (the top
+    code can clamp from 16) and the bf16 rounding of dq. An all-zero group
+    gets the smallest normal scale and q == z == 0."""
+    if group_size not in INT4_GROUP_SIZES:
+        raise ValueError(
+            f"quantize_weight_int4: group_size must be one of "
+            f"{INT4_GROUP_SIZES}, got {group_size!r}")
+    if w.dim() != 2 or w.shape[1] % group_size != 0:
+        raise ValueError(
+            f"quantize_weight_int4: need [N, K] with K % {group_size} == 0, "
+            f"got {tuple(w.shape)}")
+    wf = w.float()
+    if not bool(torch.isfinite(wf).all()):
+        raise ValueError("quantize_weight_int4: non-finite weight")
+    N, K = wf.shape
+    groups = wf.view(N, K // group_size, group_size)
+    wmin = groups.amin(dim=-1).clamp(max=0.0)
+    wmax = groups.amax(dim=-1).clamp(min=0.0)
+    tiny = 15.0 * 2.0 ** -14
+    s16 = ((wmax - wmin).clamp(min=tiny) / 15.0).clamp(
+        2.0 ** -14, 65504.0).to(torch.float16)
+    s = s16.float()
+    z = torch.round(-wmin / s).clamp(0, 15)
+    q = (torch.round(groups / s.unsqueeze(-1)) + z.unsqueeze(-1)).clamp(0, 15)
+    q = q.to(torch.uint8).view(N, K // 2, 2)
+    packed = q[..., 0] | (q[..., 1] << 4)
+    return (packed.contiguous(), s16.contiguous(),
+            z.to(torch.uint8).contiguous())
+
+
+def dequantize_int4(packed: torch.Tensor, scale: torch.Tensor,
+                    zero: torch.Tensor, group_size: int) -> torch.Tensor:
+    """The format's dq: bf16 [N, K]."""
+    from fusioninfer_amd.ops import reference
+
+    return reference.int4_dequant(packed, scale, zero, group_size)
+
+
+def _unpack_int32_nibbles(t: torch.Tensor, order) -> torch.Tensor:
+    """[R, C] int32 -> [R, 8 C] uint8: output column 8 c + order[i] is nibble
+    i (bits 4 i ... + 3) of t[:, c]."""
+    shifts = torch.arange(0, 32, 4, dtype=torch.int32)
+    nib = ((t.unsqueeze(-1) >> shifts) & 0xF).to(torch.uint8)  # [R, C, 8]
+    out = torch.empty_like(nib)
+    out[..., list(order)] = nib
+    return out.reshape(t.shape[0], -1)
+
+
+def _pack_rows(codes_nk: torch.Tensor) -> torch.Tensor:
+    N, K = codes_nk.shape
+    c = codes_nk.reshape(N, K // 2, 2)
+    return (c[..., 0] | (c[..., 1] << 4)).contiguous()
+
+
+def _check_ckpt(name, qweight, qzeros, scales):
+    if qweight.dtype != torch.int32 or qzeros.dtype != torch.int32:
+        raise ValueError(f"{name}: qweight and qzeros must be int32")
+    if scales.dtype != torch.float16:
+        raise ValueError(f"{name}: scales must be float16")
+    if qweight.dim() != 2 or qzeros.dim() != 2 or scales.dim() != 2:
+        raise ValueError(f"{name}: qweight, qzeros and scales must be 2-D")
+
+
+AWQ_ORDER = (0, 2, 4, 6, 1, 3, 5, 7)
+
+
+def int4_from_awq(qweight, qzeros, scales):
+    """AWQ (GEMM layout) -> (weight_packed, weight_scale, weight_zero).
+    qweight [K, N/8] int32, qzeros [K/G, N/8] int32, scales [K/G, N] fp16;
+    nibble i of a word holds output column 8 c + (0, 2, 4, 6, 1, 3, 5, 7)[i].
+    Pure torch on the CPU, exact."""
+    _check_ckpt("int4_from_awq", qweight, qzeros, scales)
+    K, N = qweight.shape[0], qweight.shape[1] * 8
+    ng = scales.shape[0]
+    if (ng == 0 or K % ng != 0 or tuple(scales.shape) != (ng, N)
+            or tuple(qzeros.shape) != (ng, N // 8)):
+        raise ValueError(
+            f"int4_from_awq: inconsistent shapes qweight "
+            f"{tuple(qweight.shape)}, qzeros {tuple(qzeros.shape)}, scales "
+            f"{tuple(scales.shape)}")
+    codes = _unpack_int32_nibbles(qweight.cpu(), AWQ_ORDER)  # [K, N]
+    zeros = _unpack_int32_nibbles(qzeros.cpu(), AWQ_ORDER)   # [K/G, N]
+    return (_pack_rows(codes.t().contiguous()),
+            scales.cpu().t().contiguous(), zeros.t().contiguous())
+
+
+def check_trivial_g_idx(g_idx, group_size: int, what: str) -> None:
+    """Raise ValueError unless g_idx[k] == k // group_size for every k."""
+    g = g_idx.cpu().to(torch.int64).view(-1)
+    if not torch.equal(g, torch.arange(g.numel()) // group_size):
+        raise ValueError(
+            f"{what}: g_idx is not k // group_size: act-order (desc_act) "
+            "checkpoints are not supported")
+
+
+def int4_from_gptq(qweight, qzeros, scales, g_idx=None):
+    """GPTQ (v1) -> (weight_packed, weight_scale, weight_zero). qweight
+    [K/8, N] int32 with nibble i of word r holding k = 8 r + i, qzeros
+    [K/G, N/8] int32 sequential along N and stored as z - 1, scales [K/G, N]
+    fp16. `g_idx` must be None or the trivial k // G: act-order checkpoints
+    are refused. A stored zero of 15 (z = 16) is not representable and raises.
+    Pure torch on the CPU, exact."""
+    _check_ckpt("int4_from_gptq", qweight, qzeros, scales)
+    K, N = qweight.shape[0] * 8, qweight.shape[1]
+    ng = scales.shape[0]
+    if (ng == 0 or K % ng != 0 or tuple(scales.shape) != (ng, N) or N % 8 != 0
+            or tuple(qzeros.shape) != (ng, N // 8)):
+        raise ValueError(
+            f"int4_from_gptq: inconsistent shapes qweight "
+            f"{tuple(qweight.shape)}, qzeros {tuple(qzeros.shape)}, scales "
+            f"{tuple(scales.shape)}")
+    if g_idx is not None:
+        check_trivial_g_idx(g_idx, K // ng, "int4_from_gptq")
+    seq = tuple(range(8))
+    # [N, K/8] words along K -> codes [N, K]
+    codes = _unpack_int32_nibbles(qweight.cpu().t().contiguous(), seq)
+    zeros = _unpack_int32_nibbles(qzeros.cpu(), seq).to(torch.int32) + 1
+    if int(zeros.max()) > 15:
+        raise ValueError(
+            "int4_from_gptq: a stored zero point of 15 means z = 16, which "
+            "the int4 format cannot hold")
+    return (_pack_rows(codes), scales.cpu().t().contiguous(),
+            zeros.to(torch.uint8).t().contiguous())
+
+
+def _int4_layers(module: nn.Module, group_size: int):
+    """The projection layers of a CausalLM, after checking every shard."""
+    from fusioninfer_amd.distributed.layers import (
+        MergedColumnParallelLinear,
+        RowParallelLinear,
+    )
+
+    if group_size not in INT4_GROUP_SIZES:
+        raise ValueError(
+            f"int4: group_size must be one of {INT4_GROUP_SIZES}, got "
+            f"{group_size!r}")
+    layers = [
+        m for m in module.modules()
+        if isinstance(m, (MergedColumnParallelLinear, RowParallelLinear))
+    ]
+    for m in layers:  # reject before anything is converted
+        N, K = m.weight.shape
+        if K % 128 != 0 or N % 16 != 0:
+            what = ("in_per_rank" if isinstance(m, RowParallelLinear)
+                    else "in_features")
+            raise ValueError(
+                f"int4: {type(m).__name__} shard [{N}, {K}] is unsupported: "
+                f"{what} must be a multiple of 128 and the output rows a "
+                "multiple of 16")
+    return layers
+
+
+def convert_linear_to_int4(module: nn.Module, group_size: int = 128,
+                           quantize: bool = True) -> int:
+    """Convert every projection Linear in a CausalLM to int4 storage:
+    `weight` is replaced by the buffers `weight_packed` [N, K/2],
+    `weight_scale` [N, K/G] fp16 and `weight_zero` [N, K/G] and the bf16
+    tensor is freed. Returns the number of converted layers.
+    lm_head/embedding stay bf16. One bf16 scratch, sized to the largest
+    layer, is reserved for the batches above INT4_MAX_M rows.
+
+    With quantize=False the buffers are allocated but left unfilled, for a
+    loader that copies pre-quantised checkpoint tensors into them
+    (models/weight_loader.py)."""
+    layers = _int4_layers(module, group_size)
+    scratch = _Mxfp4Scratch()
+    if layers and layers[0].weight.is_cuda:
+        scratch.reserve(max(m.weight.numel() for m in layers),
+                        layers[0].weight.device)
+    for m in layers:
+        w = m.weight.data
+        N, K = w.shape
+        if quantize:
+            packed, scale, zero = quantize_weight_int4(w, group_size)
+            validate_int4_scales(scale, zero)
+        else:
+            packed = torch.zeros((N, K // 2), dtype=torch.uint8,
+                                 device=w.device)
+            scale = torch.ones((N, K // group_size), dtype=torch.float16,
+                               device=w.device)
+            zero = torch.zeros((N, K // group_size), dtype=torch.uint8,
+                               device=w.device)
+        del m.weight
+        m.register_buffer("weight_packed", packed, persistent=False)
+        m.register_buffer("weight_scale", scale, persistent=False)
+        m.register_buffer("weight_zero", zero, persistent=False)
+        m.int4_group_size = group_size
+        m.forward = _make_int4_forward(m, scratch, group_size)
+    return len(layers)
+
+
+def _make_int4_forward(m, scratch, group_size):
+    from fusioninfer_amd import ops
+
+    is_row_parallel = hasattr(m, "in_per_rank")
+    bias = getattr(m, "bias", None)
+    N, K = m.weight_packed.shape[0], m.weight_packed.shape[1] * 2
+
+    def fwd(x):
+        x = x.contiguous()
+        if x.is_cuda and x.shape[0] > INT4_MAX_M:
+            w = ops.int4_dequant(m.weight_packed, m.weight_scale,
+                                 m.weight_zero, group_size,
+                                 out=scratch.view(N, K))
+            out = F.linear(x, w, bias)
+        else:
+            out = ops.int4_linear(x, m.weight_packed, m.weight_scale,
+                                  m.weight_zero, group_size, bias)
         if is_row_parallel:
             out = ps.tp_all_reduce(out)
         return out

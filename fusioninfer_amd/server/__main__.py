@@ -37,8 +37,16 @@ def parse_args(argv=None):
                    help='JSON: {"kv_connector": "RcclConnector", '
                         '"kv_role": "kv_producer"|"kv_consumer"}')
     p.add_argument("--enforce-eager", action="store_true")
-    p.add_argument("--quantization", choices=["fp8", "mxfp4"],
+    p.add_argument("--quantization", choices=["fp8", "mxfp4", "int4"],
                    default=None)
+    p.add_argument("--int4-group-size", type=int, choices=[32, 64, 128],
+                   default=128,
+                   help="with --quantization int4 (AWQ / GPTQ style weights: "
+                        "4-bit codes with one fp16 scale and one zero point "
+                        "per group): input channels per group when bf16 "
+                        "weights are quantised at load. An AWQ or GPTQ "
+                        "checkpoint selects int4 and its own group size. "
+                        "Dense models only")
     p.add_argument("--mxfp4-moe-experts", action="store_true",
                    help="with --quantization mxfp4 on an MoE model: store "
                         "the experts as MXFP4 too (4.25 bits per weight) and "
@@ -165,6 +173,7 @@ def build_engine_config(args):
     mc = get_model_config(args.model)
     mc.model_path = args.model_path
     mc.quantization = args.quantization
+    mc.int4_group_size = args.int4_group_size
     mc.mxfp4_moe_experts = args.mxfp4_moe_experts
     mc.mxfp4_activations = args.mxfp4_activations
     mc.mxfp4_moe_activations = args.mxfp4_moe_activations

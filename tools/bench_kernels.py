@@ -1101,6 +1101,112 @@ def bench_mxfp4(rounds=3):
                   flush=True)
 
 
+def bench_int4(rounds=3, group_size=128):
+    """The four Qwen3-8B projections at decode batch sizes: int4_linear,
+    int4_dequant + F.linear, bf16 F.linear and mxfp4_linear, alternating in
+    one process. Median device-event time of 100 calls per repetition; every
+    repetition is printed, because INT4_MAX_M is the largest M at which
+    int4_linear beats dequant + F.linear on all four layers in every one of
+    them (last column: fastest dequant + F.linear repetition over the
+    slowest int4_linear one; above 1 it won every time)."""
+    import torch.nn.functional as F
+
+    from fusioninfer_amd import ops
+    from fusioninfer_amd.quantization import (
+        quantize_weight_int4, quantize_weight_mxfp4)
+
+    shapes = [("qkv", 6144, 4096), ("o", 4096, 4096),
+              ("gate_up", 24576, 4096), ("down", 4096, 12288)]
+    G = group_size
+    print(f"\n## int4 W4A16 projections (Qwen3-8B shapes, G = {G}, median us "
+          f"of each of {rounds} repetitions)")
+    print("| layer NxK | M | int4_linear | dequant+linear | bf16 linear | "
+          "mxfp4_linear | bf16/int4_linear | dequant fastest / int4_linear "
+          "slowest |")
+    print("|---|---|---|---|---|---|---|---|")
+    for name, N, K in shapes:
+        w = torch.randn(N, K, device="cuda", dtype=torch.bfloat16) * 0.02
+        p, s, z = quantize_weight_int4(w, G)
+        mp, ms = quantize_weight_mxfp4(w)
+        scratch = torch.empty(N, K, device="cuda", dtype=torch.bfloat16)
+        for M in (1, 8, 16, 32, 64, 128):
+            x = torch.randn(M, K, device="cuda", dtype=torch.bfloat16)
+            out = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
+
+            def dq_linear():
+                ops.int4_dequant(p, s, z, G, out=scratch)
+                return F.linear(x, scratch)
+
+            fns = [
+                lambda: ops.int4_linear(x, p, s, z, G, out=out),
+                dq_linear,
+                lambda: F.linear(x, w),
+                lambda: ops.mxfp4_linear(x, mp, ms, out=out),
+            ]
+            meds = [[] for _ in fns]
+            for _ in range(rounds):
+                for i, fn in enumerate(fns):
+                    for _ in range(10):
+                        fn()
+                    meds[i].append(_median(_event_times_us(fn, 100)))
+            cells = [" / ".join(f"{u:.1f}" for u in m) for m in meds]
+            print(f"| {name} {N}x{K} | {M} | " + " | ".join(cells)
+                  + f" | {_median(meds[2]) / _median(meds[0]):.2f}x"
+                  + f" | {min(meds[1]) / max(meds[0]):.2f}x |", flush=True)
+
+
+def bench_int4_e2e(runs=3):
+    """Decode step time of Qwen3-8B (36 layers, random weights, hipGraph
+    decode) in bf16, mxfp4 and int4 at 1, 8 and 64 sequences: 64-token
+    prompts, 48 generated tokens, median wall time of the pure-decode steps
+    (synchronised per step); runs alternate between the three engines."""
+    from fusioninfer_amd.config import (CacheConfig, EngineConfig,
+                                        SchedulerConfig)
+    from fusioninfer_amd.engine.llm_engine import LLMEngine
+    from fusioninfer_amd.engine.sequence import SamplingParams
+    from fusioninfer_amd.models.registry import get_model_config
+
+    def engine(quant):
+        mc = get_model_config("Qwen3-8B")
+        mc.quantization = quant
+        cfg = EngineConfig(
+            model=mc, cache=CacheConfig(num_gpu_blocks=1024),
+            scheduler=SchedulerConfig(
+                max_num_seqs=64, max_num_batched_tokens=8192,
+                max_model_len=1024),
+            seed=7)
+        return LLMEngine(cfg, device="cuda:0")
+
+    engines = {str(q): engine(q) for q in (None, "mxfp4", "int4")}
+
+    def run(eng, n):
+        sp = SamplingParams(max_tokens=48, temperature=0.0, ignore_eos=True)
+        for i in range(n):
+            eng.add_request([(7 * i + j) % 1000 + 5 for j in range(64)], sp)
+        times = []
+        while eng.has_unfinished():
+            g0 = eng.num_generated_tokens
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            eng.step()
+            torch.cuda.synchronize()
+            if eng.num_generated_tokens - g0 == n:
+                times.append(time.perf_counter() - t0)
+        return _median(times[1:]) * 1e3  # drop the step the prefill made
+
+    print("\n## Qwen3-8B decode step (ms), bf16 / mxfp4 / int4")
+    print("| mode | run | 1 seq | 8 seqs | 64 seqs |")
+    print("|---|---|---|---|---|")
+    for eng in engines.values():
+        for n in (1, 8, 64):
+            run(eng, n)  # untimed: graph capture
+    for i in range(runs):
+        for mode, eng in engines.items():
+            cells = [f"{run(eng, n):.3f}" for n in (1, 8, 64)]
+            print(f"| {mode} | {i + 1} | " + " | ".join(cells) + " |",
+                  flush=True)
+
+
 def bench_mxfp4_moe(rounds=3):
     """The expert GEMM pair (gate_up with fused SwiGLU, then down) of
     Qwen3-30B-A3B (E = 128, top-8, H = 2048, I = 768) for bf16 moe_gemm,
@@ -1538,6 +1644,10 @@ if __name__ == "__main__":
         bench_bias_pipelining()
     if which in ("mxfp4", "all"):
         bench_mxfp4()
+    if which in ("int4", "all"):
+        bench_int4()
+    if which in ("int4_e2e", "all"):
+        bench_int4_e2e()
     if which in ("mxfp4_moe", "all"):
         bench_mxfp4_moe()
     if which in ("mxfp4_moe_a8", "all"):

@@ -59,8 +59,12 @@ class ModelConfig:
     # with quantization == "int4" (AWQ / GPTQ style: unsigned 4-bit codes,
     # one fp16 scale and one zero point per group): input channels per
     # group, 32, 64 or 128. A pre-quantised checkpoint sets it from its
-    # quantization_config. Dense models only.
+    # quantization_config. An MoE model needs int4_moe_experts.
     int4_group_size: int = 128
+    # with quantization == "int4": store the MoE experts as int4 too (same
+    # group size) and run them on the grouped W4A16 GEMM. Off: an MoE model
+    # is refused in int4 mode. No effect on a dense model.
+    int4_moe_experts: bool = False
     # MoE (Qwen3-MoE family): num_experts 0 = dense MLP
     num_experts: int = 0
     num_experts_per_tok: int = 8

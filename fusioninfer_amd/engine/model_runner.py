@@ -44,6 +44,10 @@ class ModelRunner:
             raise ValueError(
                 "mxfp4_moe_experts needs quantization='mxfp4', got "
                 f"{mc.quantization!r}")
+        if mc.int4_moe_experts and mc.quantization != "int4":
+            raise ValueError(
+                "int4_moe_experts needs quantization='int4', got "
+                f"{mc.quantization!r}")
         if mc.mxfp4_activations not in ("bf16", "mxfp8"):
             raise ValueError(
                 "mxfp4_activations must be 'bf16' or 'mxfp8', got "
@@ -67,7 +71,8 @@ class ModelRunner:
             # converts them too; opt-in)
             raise ValueError("mxfp4 does not cover MoE experts yet")
         if mc.quantization == "int4":
-            if mc.is_moe:
+            if mc.is_moe and not mc.int4_moe_experts:
+                # opt-in, as for mxfp4: int4_moe_experts converts them too
                 raise ValueError("int4 does not cover MoE experts")
             if mc.int4_group_size not in (32, 64, 128):
                 raise ValueError(
@@ -159,6 +164,15 @@ class ModelRunner:
 
                 assert convert_linear_to_int4(
                     self.model, mc.int4_group_size) > 0
+                if mc.is_moe:
+                    from fusioninfer_amd.quantization import (
+                        convert_moe_experts_to_int4,
+                    )
+
+                    # drops the experts' bf16 weights and MFMA pack before
+                    # the KV cache is sized
+                    assert convert_moe_experts_to_int4(
+                        self.model, mc.int4_group_size) > 0
         if mc.quantization not in (None, "fp8", "mxfp4", "int4"):
             raise ValueError(f"unknown quantization {mc.quantization!r}")
         spec = getattr(cfg, "speculative", None)

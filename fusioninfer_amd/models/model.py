@@ -44,6 +44,16 @@ _FUSED_ROPE_CACHE = os.environ.get("FI_FUSED_ROPE_CACHE", "1") != "0"
 MXFP4_MOE_WIDE_LO = int(os.environ.get("FI_MXFP4_MOE_WIDE_LO", "8"))
 MXFP4_MOE_WIDE_HI = int(os.environ.get("FI_MXFP4_MOE_WIDE_HI", "64"))
 
+# int4 experts: routed rows per local expert from which ops.moe_gemm_int4
+# runs at block_m 128 instead of 16 (MoEMLP._forward_int4_grouped). Measured
+# on the Qwen3-30B-A3B expert shapes (profiles/r20_int4_moe.md): at 4 rows per
+# expert block_m 16 wins (149 us against 245 us for the gate_up + down pair),
+# at 32 rows block_m 128 wins (240 us against 392 us) and keeps winning above.
+# 32 is the smallest measured size at which it wins; between 4 and 32 nothing
+# was measured. The MXFP4 rule is 256: its block_m 128 instance has no LDS A
+# panel.
+INT4_MOE_BLOCK_M_ROWS = 32
+
 
 class Attention(nn.Module):
     def __init__(self, cfg: ModelConfig, layer_idx: int = 0):
@@ -247,6 +257,10 @@ class MoEMLP(nn.Module):
         # gate_up_packed / gate_up_scale / down_packed / down_scale only
         self.mxfp4 = False
         self.mxfp4_activations = "bf16"  # or "mxfp8": block_m 128 batches
+        # set by quantization.convert_moe_experts_to_int4: experts live in
+        # {gate_up,down}_{packed,scale,zero} only
+        self.int4 = False
+        self.int4_group_size = 128
         H, inter = cfg.hidden_size, cfg.moe_intermediate_size
         base = torch.initial_seed() % (2**62)
         dev = torch.empty(0).device  # honor the ambient torch.device context
@@ -387,10 +401,11 @@ class MoEMLP(nn.Module):
         return ps.tp_all_reduce(out.to(torch.bfloat16))
 
     def _refuse_after_mxfp4(self, what: str):
-        if self.mxfp4:
+        if self.mxfp4 or self.int4:
+            fmt = "MXFP4" if self.mxfp4 else "int4"
             raise RuntimeError(
                 f"MoEMLP.{what}: the experts of layer {self.layer_idx} were "
-                "converted to MXFP4 and their bf16 weights dropped; expert "
+                f"converted to {fmt} and their bf16 weights dropped; expert "
                 "weights cannot be rewritten after 4-bit conversion")
 
     def invalidate_packed(self):
@@ -423,8 +438,9 @@ class MoEMLP(nn.Module):
         loader needs to write again. The runner calls this after weight
         load and BEFORE KV-cache sizing, so the freed bytes become KV
         blocks. CPU keeps the unpacked form (it IS the compute path).
-        A no-op after MXFP4 conversion: nothing bf16 is left to release."""
-        if self.mxfp4 or self.e_end == self.e_start:
+        A no-op after MXFP4 or int4 conversion: nothing bf16 is left to
+        release."""
+        if self.mxfp4 or self.int4 or self.e_end == self.e_start:
             return
         if self.fp8:
             if not self.gate_up_fp8.is_cuda or self.gate_up_fp8.numel() == 0:
@@ -694,9 +710,40 @@ class MoEMLP(nn.Module):
         ops.moe_combine(out, y, pos, topv.reshape(-1).float().contiguous())
         return ps.tp_all_reduce(out)
 
+    def _forward_int4_grouped(self, x: torch.Tensor) -> torch.Tensor:
+        """int4 experts (W4A16): the shape of _forward_grouped with the
+        grouped GEMMs reading packed 4-bit codes, fp16 scales and zero
+        points. No host sync on the GPU, so MoE decode graphs capture it
+        unchanged; on the CPU the same composition runs through the
+        reference ops."""
+        T, H = x.shape
+        E_local = self.e_end - self.e_start
+        logits = x.float() @ self.router_weight.float().T
+        topv, topi = self._router_topk(logits)
+        block_m = (128 if T * self.top_k >= INT4_MOE_BLOCK_M_ROWS * E_local
+                   else 16)
+        sorted_ids, expert_ids, n_valid, pos, PM = self._moe_align(
+            topi, block_m
+        )
+        G = self.int4_group_size
+        inter = self.down_packed.shape[2] * 2
+        act = torch.empty(PM, inter, dtype=x.dtype, device=x.device)
+        ops.moe_gemm_int4(act, x, self.gate_up_packed, self.gate_up_scale,
+                          self.gate_up_zero, G, sorted_ids, expert_ids,
+                          n_valid, block_m, gate_up=True)
+        y = torch.empty(PM, H, dtype=x.dtype, device=x.device)
+        ops.moe_gemm_int4(y, act, self.down_packed, self.down_scale,
+                          self.down_zero, G, sorted_ids, expert_ids, n_valid,
+                          block_m, gate_up=False)
+        out = torch.empty(T, H, dtype=x.dtype, device=x.device)
+        ops.moe_combine(out, y, pos, topv.reshape(-1).float().contiguous())
+        return ps.tp_all_reduce(out)
+
     def forward(self, x: torch.Tensor, lora=None) -> torch.Tensor:
         if self.mxfp4:
             return self._forward_mxfp4_grouped(x.contiguous())
+        if self.int4:
+            return self._forward_int4_grouped(x.contiguous())
         if self.fp8:
             return self._forward_fp8(x)
         if x.is_cuda:

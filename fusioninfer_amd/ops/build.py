@@ -38,6 +38,7 @@ SOURCES = [
     "moe_mxfp4_gemm.hip",
     "moe_mxfp8_gemm.hip",
     "int4_gemm.hip",
+    "moe_int4_gemm.hip",
 ]
 
 

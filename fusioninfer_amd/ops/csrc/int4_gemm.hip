@@ -27,7 +27,7 @@
 // Expansion of one dword (8 codes), 18 VALU against MXFP4's 4 converts:
 //   lo = w & 0x0f0f0f0f          byte b = q[2b]
 //   hi = w & 0xf0f0f0f0          byte b = 16 q[2b + 1]
-//   v_cvt_f32_ubyte{0..3} of each (cvt_f32_ubyte below), then
+//   v_cvt_f32_ubyte{0..3} of each (cvt_f32_ubyte in int4_common.h), then
 //   fma(q, s, -z s) and fma(16 q, s / 16, -z s), paired by the compiler into
 //   v_pk_fma_f32, and v_cvt_pk_bf16_f32 per pair: 2 + 8 + 4 + 4 in the ISA.
 // z s (4 x 11 bits), s / 16 and 16 q are exact, and q s - z s = (q - z) s is
@@ -50,73 +50,11 @@
 
 #include <hip/hip_runtime.h>
 
-#include "common.h"
+#include "int4_common.h"
 
 namespace fi {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) short short8;
-typedef __attribute__((ext_vector_type(4))) float floatx4;
-typedef __attribute__((ext_vector_type(2))) float floatx2;
-typedef __attribute__((ext_vector_type(4))) u32 u32x4;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-
-// Per-run dequant constants from one fp16 scale and one zero byte
-struct GroupScale {
-  floatx2 s;    // {s, s / 16}: low-nibble and high-nibble multiplier
-  floatx2 nzs;  // {-z s, -z s}
-};
-
-FI_DEV GroupScale group_scale(u16 scale_bits, u32 zero) {
-  union {
-    u16 u;
-    _Float16 h;
-  } c;
-  c.u = scale_bits;
-  const float s = static_cast<float>(c.h);
-  const float nzs = -(static_cast<float>(zero) * s);  // exact
-  return GroupScale{floatx2{s, s * 0.0625f}, floatx2{nzs, nzs}};
-}
-
-// fp32 of byte B of v: v_cvt_f32_ubyte<B>. Written as the instruction, since
-// from `(float)((v >> 8 B) & 0xff)` the compiler splits the two nibble masks
-// into one mask per byte and converts with ubyte0 only (about 26 VALU per
-// dword instead of 18).
-template <int B>
-FI_DEV float cvt_f32_ubyte(u32 v) {
-  float f = 0.f;
-#if defined(__HIP_DEVICE_COMPILE__)
-  if constexpr (B == 0) asm("v_cvt_f32_ubyte0 %0, %1" : "=v"(f) : "v"(v));
-  if constexpr (B == 1) asm("v_cvt_f32_ubyte1 %0, %1" : "=v"(f) : "v"(v));
-  if constexpr (B == 2) asm("v_cvt_f32_ubyte2 %0, %1" : "=v"(f) : "v"(v));
-  if constexpr (B == 3) asm("v_cvt_f32_ubyte3 %0, %1" : "=v"(f) : "v"(v));
-#endif
-  return f;
-}
-
-// Eight codes of one u32 (byte b: k = 2b low nibble, k = 2b + 1 high
-// nibble) -> 8 bf16 of dq, k ascending.
-FI_DEV short8 dequant_int4x8(u32 w, const GroupScale& gs) {
-  const u32 lo = w & 0x0f0f0f0fu;
-  const u32 hi = w & 0xf0f0f0f0u;
-  const floatx2 qs[4] = {
-      {cvt_f32_ubyte<0>(lo), cvt_f32_ubyte<0>(hi)},
-      {cvt_f32_ubyte<1>(lo), cvt_f32_ubyte<1>(hi)},
-      {cvt_f32_ubyte<2>(lo), cvt_f32_ubyte<2>(hi)},
-      {cvt_f32_ubyte<3>(lo), cvt_f32_ubyte<3>(hi)}};
-  union {
-    bf16x2_t p[4];
-    short8 v;
-  } u;
-#pragma unroll
-  for (int b = 0; b < 4; ++b) {
-    const floatx2 q = qs[b];
-    const floatx2 f = __builtin_elementwise_fma(q, gs.s, gs.nzs);
-    u.p[b] = __builtin_convertvector(f, bf16x2_t);
-  }
-  return u.v;
-}
 
 // U = chunk pairs a wave keeps in flight per loop trip
 template <int MT, int NT, int U>

@@ -81,6 +81,10 @@ void launch_int4_linear(u16*, const u16*, const unsigned char*, const u16*,
                         hipStream_t);
 void launch_int4_dequant(u16*, const unsigned char*, const u16*,
                          const unsigned char*, int64_t, int, hipStream_t);
+void launch_moe_gemm_int4(u16*, const u16*, const unsigned char*, const u16*,
+                          const unsigned char*, const int*, const int*,
+                          const int*, int, int, int, int, int, bool, bool,
+                          hipStream_t);
 void launch_sample_tokens(int64_t*, const float*, const float*, const int*,
                           const float*, const float*, const int64_t*, int,
                           int, hipStream_t);
@@ -1007,6 +1011,85 @@ void int4_dequant(at::Tensor out, at::Tensor w_packed, at::Tensor w_scale,
       current_stream());
 }
 
+// grouped W4A16 GEMM on int4 experts: w_packed [E, NB, K/2] uint8, w_scale
+// [E, NB, K/G] fp16 and w_zero [E, NB, K/G] uint8, NB = 2N when gate_up;
+// a = x [T, K] (gate_up) or act [PM, K]. lds_a: the block_m 128 instance
+// stages its A panel through LDS (the default) or reads it directly
+void moe_gemm_int4(at::Tensor out, at::Tensor a, at::Tensor w_packed,
+                   at::Tensor w_scale, at::Tensor w_zero, int64_t group_size,
+                   at::Tensor sorted_ids, at::Tensor expert_ids,
+                   at::Tensor n_valid, int64_t block_m, bool gate_up,
+                   bool lds_a) {
+  CHECK_BF16_CUDA(out);
+  CHECK_BF16_CUDA(a);
+  TORCH_CHECK(out.dim() == 2 && a.dim() == 2 && out.is_contiguous() &&
+                  a.is_contiguous(),
+              "moe_gemm_int4: out and a must be 2-D and contiguous");
+  TORCH_CHECK(block_m == 16 || block_m == 128,
+              "moe_gemm_int4: block_m must be 16 or 128");
+  TORCH_CHECK(group_size == 32 || group_size == 64 || group_size == 128,
+              "moe_gemm_int4: group_size must be 32, 64 or 128");
+  const int gshift = group_size == 32 ? 0 : group_size == 64 ? 1 : 2;
+  const int64_t K = a.size(1);
+  const int64_t N = out.size(1);
+  const int64_t PM = out.size(0);
+  const int64_t NB = gate_up ? 2 * N : N;
+  TORCH_CHECK(K >= 128 && K % 128 == 0 && N >= 16 && N % 16 == 0 &&
+                  K < (1LL << 31) && NB < (1LL << 31),
+              "moe_gemm_int4: need K % 128 == 0 and N % 16 == 0");
+  TORCH_CHECK(w_packed.is_cuda() && w_scale.is_cuda() && w_zero.is_cuda() &&
+                  w_packed.scalar_type() == at::kByte &&
+                  w_scale.scalar_type() == at::kHalf &&
+                  w_zero.scalar_type() == at::kByte && w_packed.dim() == 3 &&
+                  w_scale.dim() == 3 && w_zero.dim() == 3 &&
+                  w_packed.is_contiguous() && w_scale.is_contiguous() &&
+                  w_zero.is_contiguous(),
+              "moe_gemm_int4: weights must be contiguous 3-D GPU tensors, "
+              "w_packed and w_zero uint8 and w_scale float16");
+  const int64_t E = w_packed.size(0);
+  const int64_t NG = K / group_size;
+  TORCH_CHECK(E >= 1 && w_packed.size(1) == NB && w_packed.size(2) == K / 2 &&
+                  w_scale.size(0) == E && w_scale.size(1) == NB &&
+                  w_scale.size(2) == NG && w_zero.size(0) == E &&
+                  w_zero.size(1) == NB && w_zero.size(2) == NG,
+              "moe_gemm_int4: need w_packed [E, NB, K/2] and w_scale, w_zero "
+              "[E, NB, K/group_size]");
+  TORCH_CHECK(sorted_ids.is_cuda() && expert_ids.is_cuda() &&
+                  n_valid.is_cuda() && sorted_ids.scalar_type() == at::kInt &&
+                  expert_ids.scalar_type() == at::kInt &&
+                  n_valid.scalar_type() == at::kInt &&
+                  sorted_ids.is_contiguous() && expert_ids.is_contiguous() &&
+                  n_valid.numel() == 1,
+              "moe_gemm_int4: sorted_ids, expert_ids, n_valid must be "
+              "contiguous int32 on GPU");
+  TORCH_CHECK(PM >= block_m && PM % block_m == 0 && PM < (1LL << 31),
+              "moe_gemm_int4: padded rows must be a positive multiple of "
+              "block_m");
+  TORCH_CHECK(expert_ids.numel() >= PM / block_m && sorted_ids.numel() >= PM,
+              "moe_gemm_int4: sorted_ids / expert_ids too short");
+  TORCH_CHECK(a.size(0) >= 1 && (gate_up || a.size(0) >= PM),
+              "moe_gemm_int4: a too short");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(a.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(w_packed.data_ptr()) % 16 == 0,
+              "moe_gemm_int4: a and w_packed must be 16-byte aligned");
+  const auto dev = out.get_device();
+  TORCH_CHECK(a.get_device() == dev && w_packed.get_device() == dev &&
+                  w_scale.get_device() == dev && w_zero.get_device() == dev &&
+                  sorted_ids.get_device() == dev &&
+                  expert_ids.get_device() == dev &&
+                  n_valid.get_device() == dev,
+              "moe_gemm_int4: tensors must share one device");
+  fi::launch_moe_gemm_int4(
+      bf16_ptr(out), bf16_cptr(a),
+      static_cast<const unsigned char*>(w_packed.data_ptr()),
+      static_cast<const u16*>(w_scale.data_ptr()),
+      static_cast<const unsigned char*>(w_zero.data_ptr()),
+      sorted_ids.data_ptr<int>(), expert_ids.data_ptr<int>(),
+      n_valid.data_ptr<int>(), static_cast<int>(PM / block_m),
+      static_cast<int>(K), static_cast<int>(N), gshift,
+      static_cast<int>(block_m), gate_up, lds_a, current_stream());
+}
+
 // shared checks of the ops on MXFP8 rows: q [rows, K] e4m3 and scale
 // [rows, K/32] uint8, both contiguous on one GPU
 void check_mxfp8_rows(const char* op, const at::Tensor& q,
@@ -1553,6 +1636,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "point per group; bf16 in/out, fp32 accumulation)");
   m.def("int4_dequant", &int4_dequant,
         "expand int4 group-quantised weights to bf16");
+  m.def("moe_gemm_int4", &moe_gemm_int4,
+        "grouped W4A16 GEMM over block-aligned expert segments with int4 "
+        "group-quantised expert weights (gate_up=true fuses the SwiGLU "
+        "epilogue)");
   m.def("quant_mxfp8_rows", &quant_mxfp8_rows,
         "bf16 rows -> MXFP8 (e4m3 elements, one e8m0 scale per 32 k)");
   m.def("mxfp4_mxfp8_linear", &mxfp4_mxfp8_linear,

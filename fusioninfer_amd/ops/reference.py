@@ -804,13 +804,35 @@ def moe_gemm_mxfp4(out, a, w_packed, w_scale, sorted_ids, expert_ids, n_valid,
     2N when gate_up: gate rows, then up rows). Only tiles below n_valid are
     touched; sums and the SwiGLU run in fp32 and the result is rounded to
     bf16 once."""
+    return _moe_gemm_w4a16(
+        out, a, lambda e: mxfp4_dequant(w_packed[e], w_scale[e]), sorted_ids,
+        expert_ids, n_valid, block_m, gate_up)
+
+
+def moe_gemm_int4(out, a, w_packed, w_scale, w_zero, group_size: int,
+                  sorted_ids, expert_ids, n_valid, block_m: int,
+                  gate_up: bool):
+    """Grouped W4A16 GEMM on int4 group-quantised expert weights: the CPU
+    path and the semantic reference of the HIP kernel. w_packed [E, NB, K/2],
+    w_scale and w_zero [E, NB, K/G] hold each expert in the row format of
+    int4_linear (NB = 2N when gate_up: gate rows, then up rows). The loop of
+    moe_gemm_mxfp4 on int4_dequant of each expert."""
+    return _moe_gemm_w4a16(
+        out, a,
+        lambda e: int4_dequant(w_packed[e], w_scale[e], w_zero[e], group_size),
+        sorted_ids, expert_ids, n_valid, block_m, gate_up)
+
+
+def _moe_gemm_w4a16(out, a, dequant, sorted_ids, expert_ids, n_valid,
+                    block_m: int, gate_up: bool):
+    """dequant(e) -> bf16 [NB, K] of local expert e."""
     n_tiles = int(n_valid.item())
     N = out.shape[1]
     dq = {}
     for mt in range(n_tiles):
         e = int(expert_ids[mt])
         if e not in dq:
-            dq[e] = mxfp4_dequant(w_packed[e], w_scale[e]).float()  # [NB, K]
+            dq[e] = dequant(e).float()  # [NB, K]
         rows = slice(mt * block_m, (mt + 1) * block_m)
         if gate_up:
             src = a[sorted_ids[rows].long()].float()

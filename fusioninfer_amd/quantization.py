@@ -568,6 +568,57 @@ def convert_linear_to_int4(module: nn.Module, group_size: int = 128,
     return len(layers)
 
 
+def convert_moe_experts_to_int4(module: nn.Module,
+                                group_size: int = 128) -> int:
+    """Convert the experts of every MoEMLP in a CausalLM to int4 storage, the
+    int4 counterpart of convert_moe_experts_to_mxfp4.
+
+    Each expert is quantised on its [O, I] view (the transpose of
+    gate_up_t[e] / down_t[e]) with quantize_weight_int4, one expert at a
+    time, into the buffers gate_up_packed [E, 2I, H/2], gate_up_scale and
+    gate_up_zero [E, 2I, H/G], down_packed [E, H, I/2], down_scale and
+    down_zero [E, H, I/G] (gate rows first, then up rows). hidden_size and
+    moe_intermediate_size must be multiples of 128. The bf16 parameters
+    become zero-expert stand-ins that keep shape[1:], the MFMA pack cache is
+    dropped, and `mlp.int4` / `mlp.int4_group_size` are set: nothing bf16 of
+    the experts stays resident. Returns the number of converted layers."""
+    from fusioninfer_amd.models.model import MoEMLP
+
+    if group_size not in INT4_GROUP_SIZES:
+        raise ValueError(
+            f"int4: group_size must be one of {INT4_GROUP_SIZES}, got "
+            f"{group_size!r}")
+    mlps = [m for m in module.modules() if isinstance(m, MoEMLP)]
+    for m in mlps:  # reject before anything is converted
+        if m.fp8 or m.mxfp4 or m.int4:
+            raise ValueError(
+                f"int4: the experts of layer {m.layer_idx} are not bf16")
+        H, inter = m.gate_up_t.shape[1], m.down_t.shape[1]
+        if H % 128 != 0 or inter % 128 != 0:
+            raise ValueError(
+                f"int4: MoE layer {m.layer_idx} experts [hidden_size={H}, "
+                f"moe_intermediate_size={inter}] are unsupported: both must "
+                "be multiples of 128")
+    for m in mlps:
+        m.ensure_unpacked()
+        E = m.gate_up_t.shape[0]
+        for name, p in (("gate_up", m.gate_up_t), ("down", m.down_t)):
+            parts = [quantize_weight_int4(p.data[e].t().contiguous(),
+                                          group_size) for e in range(E)]
+            packed, scale, zero = (torch.stack(t) for t in zip(*parts))
+            validate_int4_scales(scale, zero)
+            m.register_buffer(f"{name}_packed", packed, persistent=False)
+            m.register_buffer(f"{name}_scale", scale, persistent=False)
+            m.register_buffer(f"{name}_zero", zero, persistent=False)
+        m._pack_cache = None
+        m._pack_version = None
+        for p in (m.gate_up_t, m.down_t):
+            p.data = p.data.new_empty((0,) + tuple(p.shape[1:]))
+        m.int4 = True
+        m.int4_group_size = group_size
+    return len(mlps)
+
+
 def _make_int4_forward(m, scratch, group_size):
     from fusioninfer_amd import ops
 

@@ -46,7 +46,14 @@ def parse_args(argv=None):
                         "per group): input channels per group when bf16 "
                         "weights are quantised at load. An AWQ or GPTQ "
                         "checkpoint selects int4 and its own group size. "
-                        "Dense models only")
+                        "An MoE model also needs --int4-moe-experts")
+    p.add_argument("--int4-moe-experts", action="store_true",
+                   help="with --quantization int4 on an MoE model: quantise "
+                        "the experts to int4 too (same group size) and run "
+                        "them on the grouped W4A16 HIP GEMM; without it an "
+                        "MoE model is refused in int4 mode. A pre-quantised "
+                        "AWQ / GPTQ MoE checkpoint is not loadable yet. "
+                        "Measurements: profiles/r20_int4_moe.md")
     p.add_argument("--mxfp4-moe-experts", action="store_true",
                    help="with --quantization mxfp4 on an MoE model: store "
                         "the experts as MXFP4 too (4.25 bits per weight) and "
@@ -174,6 +181,7 @@ def build_engine_config(args):
     mc.model_path = args.model_path
     mc.quantization = args.quantization
     mc.int4_group_size = args.int4_group_size
+    mc.int4_moe_experts = args.int4_moe_experts
     mc.mxfp4_moe_experts = args.mxfp4_moe_experts
     mc.mxfp4_activations = args.mxfp4_activations
     mc.mxfp4_moe_activations = args.mxfp4_moe_activations

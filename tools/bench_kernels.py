@@ -1303,6 +1303,104 @@ def bench_mxfp4_moe(rounds=3):
                       for k, v in nbytes.items()))
 
 
+def bench_int4_moe(rounds=3):
+    """The expert GEMM pair (gate_up with fused SwiGLU, then down) of
+    Qwen3-30B-A3B (E = 128, top-8, H = 2048, I = 768) for bf16 moe_gemm,
+    moe_gemm_mxfp4 and moe_gemm_int4 (G = 128) in one process, on the same
+    seeded random routing; alignment is excluded. Each figure is the median
+    of 100 device-event times after 10 warm-up calls; `rounds` alternating
+    rounds are taken and the fastest and slowest round median printed. From
+    T = 64 on both block_m are timed to show the crossover; at block_m 128
+    the int4 pair is timed with the A panel staged through LDS (what
+    ops.moe_gemm_int4 runs) and read directly from global memory, after the
+    two forms are checked to give the same bits."""
+    from fusioninfer_amd import ops
+    from fusioninfer_amd.ops import _C
+    from fusioninfer_amd.quantization import (
+        quantize_weight_int4, quantize_weight_mxfp4)
+
+    E, topk, H, inter, G = 128, 8, 2048, 768, 128
+    dev = "cuda"
+    g = torch.Generator(device=dev).manual_seed(0)
+
+    def draw(*shape):
+        return (torch.randn(*shape, generator=g, device=dev) * 0.02).to(
+            torch.bfloat16)
+
+    w = {}
+    for name, N, K in (("gate_up", 2 * inter, H), ("down", H, inter)):
+        oi = torch.stack([draw(N, K) for _ in range(E)])  # [E, O, I]
+        mx = [quantize_weight_mxfp4(oi[e]) for e in range(E)]
+        i4 = [quantize_weight_int4(oi[e], G) for e in range(E)]
+        w[name] = dict(
+            bf16=ops.pack_moe_weights(oi.transpose(1, 2).contiguous()),
+            mx=[torch.stack(t) for t in zip(*mx)],
+            i4=[torch.stack(t) for t in zip(*i4)],
+        )
+        del oi, mx, i4
+    gu, dn = w["gate_up"], w["down"]
+    print("\n## int4 MoE experts: gate_up + down pair, Qwen3-30B-A3B shapes, "
+          f"G = {G} (median us, fastest..slowest of {rounds} rounds)")
+    print("| T | block_m | bf16 moe_gemm | moe_gemm_mxfp4 | moe_gemm_int4 | "
+          "int4, direct A | bf16 fastest / int4 slowest | "
+          "mxfp4 fastest / int4 slowest |")
+    print("|---|---|---|---|---|---|---|---|")
+    for T in (1, 8, 64, 512, 2048, 8192):
+        x = draw(T, H)
+        logits = torch.randn(T, E, generator=g, device=dev)
+        _, topi = ops.moe_router_topk(logits, topk, True)
+        for block_m in ((16, 128) if T >= 64 else (16,)):
+            s, e, n, _, PM = ops.moe_align(topi, 0, E, block_m)
+            act = torch.empty(PM, inter, device=dev, dtype=torch.bfloat16)
+            y = torch.empty(PM, H, device=dev, dtype=torch.bfloat16)
+
+            def bf16():
+                ops.moe_gemm(act, x, gu["bf16"], s, e, n, block_m, True)
+                ops.moe_gemm(y, act, dn["bf16"], s, e, n, block_m, False)
+
+            def mxfp4():
+                ops.moe_gemm_mxfp4(act, x, *gu["mx"], s, e, n, block_m, True)
+                ops.moe_gemm_mxfp4(y, act, *dn["mx"], s, e, n, block_m, False)
+
+            def int4():
+                ops.moe_gemm_int4(act, x, *gu["i4"], G, s, e, n, block_m, True)
+                ops.moe_gemm_int4(y, act, *dn["i4"], G, s, e, n, block_m,
+                                  False)
+
+            def int4_direct():
+                _C.moe_gemm_int4(act, x, *gu["i4"], G, s, e, n, block_m, True,
+                                 False)
+                _C.moe_gemm_int4(y, act, *dn["i4"], G, s, e, n, block_m,
+                                 False, False)
+
+            fns = {"bf16": bf16, "mxfp4": mxfp4, "int4": int4}
+            if block_m == 128:
+                fns["direct"] = int4_direct
+                int4()
+                valid = int(n) * block_m
+                staged = y[:valid].clone()
+                int4_direct()
+                assert torch.equal(y[:valid], staged), "A paths differ"
+            meds = {k: [] for k in fns}
+            for _ in range(rounds):
+                for name, fn in fns.items():
+                    for _ in range(10):
+                        fn()
+                    meds[name].append(_median(_event_times_us(fn, 100)))
+            cells = [f"{min(m):.1f}..{max(m):.1f}" for m in meds.values()]
+            if block_m == 16:
+                cells.append("-")
+            print(f"| {T} | {block_m} | " + " | ".join(cells)
+                  + f" | {min(meds['bf16']) / max(meds['int4']):.2f}x"
+                  + f" | {min(meds['mxfp4']) / max(meds['int4']):.2f}x |",
+                  flush=True)
+    active = 3 * H * inter  # weights of one expert
+    print("weight bytes per active expert: "
+          + ", ".join(f"{k} {active * v / 1e6:.2f} MB" for k, v in (
+              ("bf16", 2.0), ("mxfp4", 4.25 / 8),
+              ("int4", (4 + 24 / G) / 8))))
+
+
 def bench_mxfp4_moe_a8(rounds=3):
     """The prefill expert GEMM pair of Qwen3-30B-A3B (E = 128, top-8, H =
     2048, I = 768) at block_m 128: bf16 moe_gemm, moe_gemm_mxfp4 (W4A16) and
@@ -1650,6 +1748,8 @@ if __name__ == "__main__":
         bench_int4_e2e()
     if which in ("mxfp4_moe", "all"):
         bench_mxfp4_moe()
+    if which in ("int4_moe", "all"):
+        bench_int4_moe()
     if which in ("mxfp4_moe_a8", "all"):
         bench_mxfp4_moe_a8()
     if which in ("mxfp4_moe_a8_wide", "all"):

@@ -1,13 +1,16 @@
-"""Re-measure LOGITS_FLOOR of tests/test_mxfp4_moe_gpu.py.
+"""Re-measure LOGITS_FLOOR of tests/test_mxfp4_moe_gpu.py, or of
+tests/test_int4_moe_gpu.py when that module's name is given.
 
 The floor is the max-abs difference of the prefill logits between the bf16
 `tiny-qwen3-moe` engine on dequantised weights on the GPU and the same
 weights on the CPU reference ops, for the test's own prompts. Neither engine
-runs the MXFP4 code. Prints the figures; asserts nothing.
+runs the 4-bit code. Prints the figures; asserts nothing.
 
 Usage (from the repository root, on a GPU):
-    python tools/mxfp4_moe_logits_floor.py
+    python tools/mxfp4_moe_logits_floor.py [test_int4_moe_gpu]
 """
+
+import importlib
 
 import os
 import sys
@@ -16,7 +19,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-import test_mxfp4_moe_gpu as t  # noqa: E402
+t = importlib.import_module(
+    sys.argv[1] if len(sys.argv) > 1 else "test_mxfp4_moe_gpu")
 
 
 def cpu_copy_of(eng):
